@@ -179,6 +179,8 @@ def shape_problem(world, args):
         return "the residue-class NTT split needs a power-of-two world <= 8 (got %d)" % world
     if not args.no_config5 and ((1 << args.config5_log2n) // world) % world:
         return "config 5: G^2 must divide n (G = %d, n = 2^%d)" % (world, args.config5_log2n)
+    if args.steps < 1 or args.warmup < 0:
+        return "--steps must be >= 1 and --warmup >= 0"
     if args.log2n < 1 or args.log2n > 27:
         return "--log2n must be 1 .. 27 (2^27 points per device is the entry format's cap)"
     return None
@@ -283,9 +285,10 @@ def promote_config5(out, c5, args, world, dist, one_device):
     lg = args.config5_log2n
     n = 1 << lg
     pr = t["per_rank"]
+    timed_steps = t["steps"] * len(t["blocks_ms"])  # blocks of `steps` steps
     out["strong_scaling"] = {"workload": "BASELINE config 5: per step ONE 2^%d-point MSM + ONE 2^%d coset NTT, sharded over the N GPUs" % (lg, lg),
                              "n_gpus": world, "value": t["value_mscalar_per_s"], "unit": "Mscalar-mults/s", "ms_per_step": t["ms_per_step"],
-                             "ntt_gfield_ops_per_s": t["ntt_gfield_ops_per_s"], "steps": t["steps"], "warmup": t["warmup"],
+                             "ntt_gfield_ops_per_s": t["ntt_gfield_ops_per_s"], "steps": t["steps"], "timed_steps": timed_steps, "warmup": t["warmup"],
                              "bit_exact_vs_reference": c5["bit_exact_vs_reference"]}
     if world == 1:
         return
@@ -295,7 +298,7 @@ def promote_config5(out, c5, args, world, dist, one_device):
     out["metric"] = ("BN254 G1 MSM Mscalar-mults/s (+ Fr coset-NTT Gfield-ops/s in strong_scaling) -- BASELINE config 5: n=2^%d over %d GPUs, strong scaling"
                      % (lg, world))
     out["value"], out["ms_per_step"], out["scaling"] = t["value_mscalar_per_s"], t["ms_per_step"], "strong"
-    out["steps"], out["warmup"] = t["steps"], t["warmup"]
+    out["steps"], out["timed_steps"], out["warmup"] = t["steps"], timed_steps, t["warmup"]
     out["config"]["workload"] = ("BASELINE config 5, per step: ONE 2^%d-point Pippenger MSM sharded by point range over %d GPUs (resident SRS shards; "
                                  "all-gather of the %d 96-B partials + group sum) + ONE 2^%d coset NTT sharded by residue class (one all-to-all of "
                                  "%s + a size-%d DFT across ranks)" % (lg, world, world, lg, c5["exchange"]["ntt"].replace("all_to_all ", ""), world))
@@ -319,11 +322,12 @@ def promote_config5(out, c5, args, world, dist, one_device):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="steps per timed block; the line's timed_steps = steps x blocks (--blocks 1: exactly --steps)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--blocks", type=int, default=5, help="the timed block of --steps steps is repeated this many times; the MEDIAN block is reported")
+    ap.add_argument("--blocks", type=int, default=5, help="the timed block of --steps steps is repeated this many times; the MEDIAN block is reported "
+                    "(ms_per_step = its time / --steps)")
     ap.add_argument("--no-config5", action="store_true", help="skip extra.config5 (one 2^24 MSM + one 2^24 coset NTT, strong scaling)")
     ap.add_argument("--no-prover-shaped", action="store_true", help="skip extra.prover_shaped (BASELINE config 4 on the resident prover rounds)")
     ap.add_argument("--config5-log2n", type=int, default=24)
@@ -335,6 +339,8 @@ def main():
     ap.add_argument("--limbs29", type=int, default=-1, help="A/B: bucket accumulation on 9 x 29-bit limbs (1, default) or 8 x 32 (0)")
     ap.add_argument("--acc-waves", type=int, default=-1, help="A/B: lane segments per SIMD lane of the bucket accumulation (0 = automatic)")
     ap.add_argument("--reduce-quad", type=int, default=-1, help="A/B: msm_reduce_quad stage mask (library default 14)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed to DIR/<name>.npy "
+                    "(rank 0; see dump_outputs())")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -474,6 +480,10 @@ def main():
     elapsed, prof = blocks[order[len(order) // 2]]
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * n / (elapsed / args.steps) / 1e6
+    dumped = None
+    # the step this line reports: this one at N = 1 (or without config 5); at N > 1 config 5's timed step is the headline and dumps itself
+    if args.dump_outputs and rank == 0 and (world == 1 or args.no_config5):  # before anything else runs on these buffers
+        dumped = dump_outputs(args.dump_outputs, pkg, bbg, pipe.last_result() if pipe is not None else d_result, d_coeffs_work)
 
     # ---- per-kernel numbers from the HIP events recorded inside the timed region
     def avg(name):
@@ -530,7 +540,8 @@ def main():
 
     out = {
         "metric": "BN254 G1 MSM Mscalar-mults/s (+ Fr NTT Gfield-ops/s in extra) at n=2^%d" % lg,
-        "value": round(value, 3), "unit": "Mscalar-mults/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "value": round(value, 3), "unit": "Mscalar-mults/s", "n_gpus": world, "steps": args.steps, "timed_steps": args.steps * len(blocks),
+        "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u32 limbs (256-bit Montgomery integers)", "data": "synthetic",
         "config": {"workload": "per GPU and step: 1 Pippenger MSM (n=2^%d scalars, hashed synthetic SRS resident in HBM) + 1 forward "
@@ -540,6 +551,8 @@ def main():
                                else ("RCCL (torch.distributed nccl)" if dist is not None else "none")},
         "roofline": roofline, "extra": extra,
     }
+    if dumped is not None:
+        extra["dump_outputs"] = dumped
 
     if pipe is not None:
         d_result = pipe.last_result()
@@ -624,9 +637,12 @@ def main():
         # at N = 1 it is the first point of the same series (top-level "strong_scaling")
         c5_side = (side, bbg_side) if dist is not None else None
         c5 = guarded("config5", lambda: config5(pkg, par, bbg, dist, dev, rank, world, args.config5_log2n, timed_steps=args.steps,
-                                                warmup=max(1, min(args.warmup, 3)), blocks=min(3, max(1, args.blocks)), side=c5_side), 600)
+                                                warmup=max(1, min(args.warmup, 3)), blocks=min(3, max(1, args.blocks)), side=c5_side,
+                                                dump_dir=args.dump_outputs if world > 1 else None), 600)
         if rank == 0:
             extra["config5"] = c5
+            if isinstance(c5, dict) and "dump_outputs" in c5:
+                extra["dump_outputs"] = c5.pop("dump_outputs")
             promote_config5(out, c5, args, world, dist, one_device)
     # ---- BASELINE config 2 / 3 across sizes (isolated, one GPU)
     if rank == 0 and world == 1 and not args.no_sweeps and not stuck:
@@ -646,6 +662,47 @@ def main():
     bbg.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_NTT_SAMPLE = 1 << 18  # NTT outputs dumped: a fixed, seeded sample of this many (all of them at n <= 2^18)
+
+
+def _limbs_f64(a):
+    """u64 limbs (..., L) -> float64 (..., 2L): each limb as its low and high 32-bit halves, exact in float64."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    halves = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1)
+    return halves.reshape(a.shape[:-1] + (2 * a.shape[-1],)).astype(np.float64)
+
+
+def dump_outputs(out_dir, pkg, bbg, d_result, ntt):
+    """--dump-outputs: what the timed path handed its caller in its LAST step, as float64 .npy files (every u64 limb as two 32-bit halves,
+    low half first; _limbs_f64).  The inputs are seeded, so the same arguments give the same files on every build:
+      msm_affine.npy     (16,)     the step's MSM result through bbg_g1_normalize: canonical Montgomery affine.  The Jacobian the MSM
+                                   writes is not dumped: its scaling changes from run to run.
+      ntt_index.npy      (k,)      the sampled positions of the NTT output: all n of them at n <= DUMP_NTT_SAMPLE, else a sorted, seeded sample
+      ntt_values.npy     (k, 8)    the step's NTT output at those positions, reduced to canonical Montgomery Fr (fr_reduce_once)
+    Size: 64 B per sampled value + 8 B per index, k <= 2^18: at most 18 MB in all.  `ntt` is the whole (n, 4)-limb output, on the device
+    (torch tensor) or on the host (numpy).  The NTT is applied to its own output once per step, warmup and every timed block included, so the
+    values depend on --warmup, --steps and --blocks."""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    n = ntt.numel() // 4 if isinstance(ntt, torch.Tensor) else ntt.size // 4
+    jac = d_result.cpu().numpy().view(np.uint64).reshape(12).copy()
+    if n <= DUMP_NTT_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(SEED).choice(n, DUMP_NTT_SAMPLE, replace=False)).astype(np.int64)
+    if isinstance(ntt, torch.Tensor):
+        rows = ntt.view(-1, 4)[torch.from_numpy(idx).to(ntt.device)].cpu().numpy().view(np.uint64)
+    else:
+        rows = np.ascontiguousarray(ntt, dtype=np.uint64).reshape(-1, 4)[idx]
+    arrays = {"msm_affine": _limbs_f64(bbg.g1_normalize(jac).reshape(8)),
+              "ntt_index": idx.astype(np.float64), "ntt_values": _limbs_f64(pkg.fr_reduce_once(rows))}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {k + ".npy": list(a.shape) for k, a in arrays.items()},
+            "encoding": "float64; every u64 limb as [low 32 bits, high 32 bits]"}
 
 
 def step_issue_floor():
@@ -773,7 +830,7 @@ def msm_sweep(pkg, bbg, dev, sizes=(16, 20, 22, 24)):
             "sizes": rows}
 
 
-def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, warmup=1, blocks=1, side=None):
+def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, warmup=1, blocks=1, side=None, dump_dir=None):
     """BASELINE config 5 -- one 2^lg MSM (point-range shards, all-gather of the 96-byte partials + group sum) and one 2^lg coset NTT
     (residue-class shards, one all-to-all, size-N DFT) over the N ranks, inputs resident, STRONG scaling (total work fixed as N grows).
 
@@ -781,6 +838,8 @@ def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, w
     contract's timed region on THIS workload: `warmup` untimed steps, then `blocks` blocks of exactly K steps (1 sharded MSM + 1 sharded
     coset NTT each) between two fences (pipeline flush + barrier + synchronize), max over ranks, median block -> `timed` (the N > 1
     headline of the line: value = 2^lg / seconds per step).  `side` = (stream, context): the exchange of earlier MSMs' partials runs there.
+    `dump_dir`: after the timed region, rank 0 writes the last timed step's MSM result and the whole transform (gathered in natural order)
+    there (dump_outputs).
 
     Self-checking: the inputs are the seeded ones of tests/golden/msm24.json (hashed SRS 0xBB254, synthetic_scalars(0xBB254 + 24))
     and tests/golden/ntt_large.json (synthetic_scalars(900 + lg), op coset_fft), both recorded from the compiled REFERENCE, so at
@@ -902,6 +961,10 @@ def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, w
                  "ntt_gfield_ops_per_s": round(1.5 * n * lg / (el / timed_steps) / 1e9, 2),
                  "per_rank": {"points": count, "msm_window_bits": width, "msm_windows": windows, "accumulate_avg_launch_ms": round(acc_ms, 4),
                               "phase_ms_per_step": {k: round(v[0] / timed_steps, 4) for k, v in pr.items()}}}
+        if dump_dir:  # every rank enters the gather
+            nat = par.gather_natural_order(dist, last["ntt"], lg)
+            if rank == 0:
+                dumped = dump_outputs(dump_dir, pkg, bbg, tpipe.last_result(), nat)
     # ---- self-check against the reference's recorded results (after the timed regions; the legs are re-run on the recorded inputs)
     check = {"msm": None, "ntt": None, "source": "tests/golden/msm24.json, ntt_large.json, config5_small.json (compiled reference)"}
     if timed is not None:
@@ -925,6 +988,8 @@ def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, w
            "exchange": {"msm": "all_gather %d x 96 B" % world, "ntt": "all_to_all %.1f MiB per rank" % (32.0 * m * (world - 1) / world / 2**20)}}
     if timed is not None:
         res["timed"] = timed
+        if dump_dir and rank == 0:
+            res["dump_outputs"] = dumped
     return res
 
 

@@ -1278,17 +1278,29 @@ def test_shim_reference_api_on_gpu():
     assert r.returncode == 0 and "shim_check PASS" in out, out
 
 
-def test_bench_contract_and_dist_path():
+def _dumped_u64(a):
+    """bench.py --dump-outputs stores every u64 limb as two float64 32-bit halves, low half first: the limbs back."""
+    h = a.astype(np.uint64).reshape(-1, 2)
+    assert np.array_equal(h.astype(np.float64), a.reshape(-1, 2)) and np.all(h < (1 << 32))
+    return h[:, 0] | (h[:, 1] << np.uint64(32))
+
+
+def test_bench_contract_and_dist_path(tmp_path):
     """bench.py prints one JSON line with the contract's fields; BBG_FORCE_DIST=1 drives the RCCL all-gather +
-    software-pipelined sharded-MSM path (world of 1) and the result must still be bit-exact against the CPU reference."""
+    software-pipelined sharded-MSM path (world of 1) and the result must still be bit-exact against the CPU reference.
+    The line counts its timed steps (--steps per block x --blocks), and --dump-outputs writes the last step's MSM point and NTT output: the
+    point the CPU oracle computes, and the oracle's transform applied once per warm-up and timed step."""
     import json
     import os
     import subprocess
     import sys
+    import __graft_entry__ as ge
+    from oracle.oracle import Oracle
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BBG_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     env.pop("MASTER_PORT", None)  # bench.py picks a free port for its world of one: two suites on one box cannot collide
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--log2n", "16", "--config5-log2n", "18", "--real-prover-log2", "10"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--log2n", "16", "--config5-log2n", "18",
+                        "--real-prover-log2", "10", "--dump-outputs", str(tmp_path / "dump")], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -1299,6 +1311,9 @@ def test_bench_contract_and_dist_path():
     assert out["cpu_baseline"]["gpu_bit_exact_vs_cpu"] is True
     assert out["roofline"]["frac"] > 0 and out["value"] > 0
     assert len(out["extra"]["timed_blocks_ms"]) == 5 and abs(out["ms_per_step"] * 3 - sorted(out["extra"]["timed_blocks_ms"])[2]) < 1e-2
+    assert out["steps"] == 3 and out["timed_steps"] == 3 * 5  # default --blocks 5
+    c5t = out["extra"]["config5"]["timed"]  # config 5: min(3, --blocks) blocks of --steps steps
+    assert c5t["steps"] == 3 and len(c5t["blocks_ms"]) == 3 and out["strong_scaling"]["timed_steps"] == 3 * 3
     assert out["extra"]["prover_shaped"]["proof_ms"] > 0 and out["extra"]["config5"]["msm_ms"] > 0 and out["extra"]["config5"]["ntt_ms"] > 0
     # N = 1: the headline stays BASELINE's metric; the strong-scaling series' first point sits beside it
     assert out["scaling"] == "weak" and out["strong_scaling"]["n_gpus"] == 1 and out["strong_scaling"]["value"] > 0
@@ -1308,10 +1323,27 @@ def test_bench_contract_and_dist_path():
     if rp is not None and "error" not in rp:  # oracle/_ref prover libraries shipped: the real reference prover, CPU vs link-time shim
         assert rp["byte_identical_to_cpu_proof"] is True and rp["verified"] == [1, 1, 1, 1] and rp["wrapped_zero_edits_ms"] < rp["link_only_ms"]
         assert out["extra"]["host_path"]["shim_linked_proof_ms"]["construct_proof_wrapped_too"] == rp["wrapped_zero_edits_ms"]
+    # the dumped outputs: float64 halves of u64 limbs; the affine point is the MSM the CPU reference checked (inputs as bench.py seeds them)
+    dump = {k: np.load(tmp_path / "dump" / (k + ".npy")) for k in ("msm_affine", "ntt_index", "ntt_values")}
+    assert out["extra"]["dump_outputs"]["files"] == {k + ".npy": list(a.shape) for k, a in dump.items()}
+    assert all(a.dtype == np.float64 for a in dump.values())
+    assert dump["msm_affine"].shape == (16,) and dump["ntt_values"].shape == (1 << 16, 8)
+    assert np.array_equal(dump["ntt_index"], np.arange(1 << 16))
+    oracle = Oracle()
+    pkg = ge.load_package()
+    n = 1 << 16
+    want = oracle.pippenger(pkg.synthetic_scalars(0xBB254 + 3, n), oracle.srs_hashed(0xBB254, n))
+    assert np.array_equal(_dumped_u64(dump["msm_affine"]), want)
+    want = pkg.synthetic_scalars(0xBB254 + 100 + 16, n)  # bench.py's coefficients: one forward NTT in place per step, 1 warm-up + 15 timed
+    for _ in range(1 + out["timed_steps"]):
+        want = oracle.ntt(want, 0)
+    assert np.array_equal(_dumped_u64(dump["ntt_values"]).reshape(-1, 4), want)
 
 
-@pytest.mark.parametrize("world", [2, 8])
-def test_bench_self_launched_ranks_one_device_rehearsal(world):
+# at most 6 processes may hold a GPU open at once on a shared machine: this suite's own process (the session context) + 4 ranks stays
+# under it; world 8's shapes (G = 8 residue classes, eight cosets, depth-4 pipeline) run in tests/test_distributed_cpu.py over gloo
+@pytest.mark.parametrize("world", [2, 4])
+def test_bench_self_launched_ranks_one_device_rehearsal(world, tmp_path, pkg, oracle):
     """`python bench.py --gpus N` started WITHOUT a launcher (WORLD_SIZE unset): bench.py starts its N ranks itself, and with
     BBG_DIST_ONE_DEVICE=1 all of them share device 0 and exchange through gloo with host staging (parallel.HostStagedDist) -- the whole
     N-rank bench on real kernels: ShardedMsmPipeline at depth 4 with its side stream and side context per rank, the max-over-ranks
@@ -1327,7 +1359,8 @@ def test_bench_self_launched_ranks_one_device_rehearsal(world):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "BBG_FORCE_DIST")}
     env.update(BBG_DIST_ONE_DEVICE="1", BBG_BENCH_LAUNCH_TIMEOUT="800")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--blocks", "2",
-                        "--log2n", "14", "--config5-log2n", "16"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--log2n", "14", "--config5-log2n", "16", "--dump-outputs", str(tmp_path / "dump")], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=900)
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, lines, r.stderr.decode()[-3000:])
     out = json.loads(lines[0])
@@ -1345,10 +1378,33 @@ def test_bench_self_launched_ranks_one_device_rehearsal(world):
     assert out["roofline"]["avg_launch_ms"] > 0 and out["roofline"]["algorithmic_bytes"] == 96.0 * ((1 << 16) // world)
     c5 = out["extra"]["config5"]
     assert len(c5["timed"]["blocks_ms"]) == 2 and c5["timed"]["steps"] == 6
+    assert out["steps"] == 6 and out["timed_steps"] == out["strong_scaling"]["timed_steps"] == 6 * 2
     assert c5["n_gpus"] == world and c5["msm_ms"] > 0 and c5["ntt_ms"] > 0, c5
     assert c5["bit_exact_vs_reference"]["msm"] is True and c5["bit_exact_vs_reference"]["ntt"] is True, c5
     assert c5["exchange"]["msm"] == "all_gather %d x 96 B" % world and not c5["exchange"]["ntt"].startswith("all_to_all 0.0"), c5
     assert "cpu_baseline" not in out  # rank 0 runs the CPU leg at N = 1 only
+    # N > 1: --dump-outputs writes config 5's last timed step (the headline): the MSM the reference recorded, and the whole 2^16 transform
+    dump = {k: np.load(tmp_path / "dump" / (k + ".npy")) for k in ("msm_affine", "ntt_index", "ntt_values")}
+    assert out["extra"]["dump_outputs"]["files"] == {k + ".npy": list(a.shape) for k, a in dump.items()}
+    rec = [r for r in json.load(open(os.path.join(root, "tests", "golden", "config5_small.json")))["sizes"] if r["log2n"] == 16][0]
+    assert np.array_equal(_dumped_u64(dump["msm_affine"]), np.frombuffer(bytes.fromhex(rec["msm_result"]), dtype=np.uint64))
+    n, G = 1 << 16, world
+    m = n // G
+    assert np.array_equal(dump["ntt_index"], np.arange(n))
+    # 2 warm-up + 12 timed steps, each a sharded coset_fft of what rank g's buffer holds (parallel.ntt_sharded): its residue class a[g + G j]
+    # in, and after the step the local transform Z_g[q] = sum_j a[g + G j] c^(g + G j) w_n^((g + G j) q), q < m -- residue class g's share
+    # of the coset transform, i.e. the coset_fft of a with every other class zeroed, at its first m points.  The last step's output (the
+    # whole transform of its input, gathered in natural order) is what is dumped.
+    a = pkg.synthetic_scalars(900 + 16, n)
+    for _ in range(2 + out["timed_steps"] - 1):
+        nxt = np.empty_like(a)
+        for g in range(G):
+            b = np.zeros_like(a)
+            b[g::G] = a[g::G]
+            nxt[g::G] = oracle.ntt(b, 2)[:m]
+        a = nxt
+    A = oracle.ntt(a, 2)
+    assert np.array_equal(_dumped_u64(dump["ntt_values"]).reshape(-1, 4), A)
 
 
 @pytest.mark.parametrize("lg", [25, 26, 27, 28])
