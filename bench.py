@@ -15,9 +15,14 @@ built once, like compute_lookup_table).  `value` = scalars processed by all rank
     BBG_DIST_ONE_DEVICE=1 python bench.py --gpus N ...   (REHEARSAL: all N ranks on device 0, exchanges staged through the host over gloo --
                                                           the whole N-rank code path on one GPU; its timings say nothing about xGMI)
 
-Rank 0 prints ONE JSON line.  At N = 1, rank 0 also runs the CPU baseline on the host cores (the real reference
-binary oracle/_ref/libbbref.so when it runs on this CPU, else the oracle port) on a bounded sample, and checks the GPU
-results bit-exactly against it.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, warm-up, the timed blocks,
+--dump-outputs, and the figures derived from the timed blocks' own events and the committed profiles.  Everything that takes
+runs of its own is behind --full:
+    python bench.py --gpus 1 --full ...
+At N = 1 that is the CPU baseline on the host cores (the real reference binary oracle/_ref/libbbref.so when it runs on
+this CPU, else the oracle port) on a bounded sample, with the GPU results checked bit-exactly against it, the prover-shaped
+sequence, the host-buffer entry points, config 5 (strong_scaling) and the size sweeps.  At N > 1 config 5 is the headline and
+runs either way; --full adds its separately timed legs and its check against the reference's recorded results.
 """
 import argparse
 import json
@@ -325,15 +330,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="steps per timed block; the line's timed_steps = steps x blocks (--blocks 1: exactly --steps)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what takes runs of its own beside the headline: the CPU baseline, the prover-shaped "
+                    "sequence, the host-buffer entry points, config 5 at N = 1 (its legs and reference check at N > 1) and the size sweeps; the --no-* "
+                    "options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--blocks", type=int, default=5, help="the timed block of --steps steps is repeated this many times; the MEDIAN block is reported "
                     "(ms_per_step = its time / --steps)")
-    ap.add_argument("--no-config5", action="store_true", help="skip extra.config5 (one 2^24 MSM + one 2^24 coset NTT, strong scaling)")
-    ap.add_argument("--no-prover-shaped", action="store_true", help="skip extra.prover_shaped (BASELINE config 4 on the resident prover rounds)")
+    ap.add_argument("--no-config5", action="store_true", help="skip extra.config5 (one 2^24 MSM + one 2^24 coset NTT, strong scaling): at N = 1 with "
+                    "--full; at N > 1 the headline is then the per-GPU step")
+    ap.add_argument("--no-prover-shaped", action="store_true", help="--full: skip extra.prover_shaped (BASELINE config 4 on the resident prover rounds)")
     ap.add_argument("--config5-log2n", type=int, default=24)
-    ap.add_argument("--real-prover-log2", type=int, default=16, help="cpu_baseline.real_prover: gates of the reference TurboPLONK circuit proved on the host "
-                    "cores and through the link-time shim (0 = skip; 2^20 takes ~1 min of circuit construction)")
-    ap.add_argument("--no-sweeps", action="store_true", help="skip extra.host_path / extra.ntt_sweep / extra.msm_sweep (SURVEY 8d tables)")
+    ap.add_argument("--real-prover-log2", type=int, default=16, help="--full: cpu_baseline.real_prover: gates of the reference TurboPLONK circuit proved on "
+                    "the host cores and through the link-time shim (0 = skip; 2^20 takes ~1 min of circuit construction)")
+    ap.add_argument("--no-sweeps", action="store_true", help="--full: skip extra.host_path / extra.ntt_sweep / extra.msm_sweep (SURVEY 8d tables)")
     ap.add_argument("--reduce-priority", type=int, default=-1, help="A/B: 1 = low-priority auxiliary stream for the MSM reduce phase (library default), 0 = normal")
     ap.add_argument("--msm-window", type=int, default=0, help="bucket window width: 0 = library default, or a compiled width (A/B runs)")
     ap.add_argument("--limbs29", type=int, default=-1, help="A/B: bucket accumulation on 9 x 29-bit limbs (1, default) or 8 x 32 (0)")
@@ -557,7 +566,7 @@ def main():
     if pipe is not None:
         d_result = pipe.last_result()
     # ---- CPU baseline + bit-exact check against it (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pkg, bbg, srs, scalars, coeffs, d_result, d_coeffs, lg, value)
         if args.real_prover_log2 and out["cpu_baseline"].get("kind") == "reference":
             try:  # main thread only: the reference's OpenMP state (see reference_prover_sequence below)
@@ -589,7 +598,7 @@ def main():
         return box["value"] if "value" in box else {"error": box.get("error", "no result")}
 
     # ---- BASELINE config 4 (TurboPLONK prover sequence) on the resident prover rounds, one GPU
-    if rank == 0 and world == 1 and not args.no_prover_shaped and lg >= 10:
+    if rank == 0 and world == 1 and args.full and not args.no_prover_shaped and lg >= 10:
         extra["prover_shaped"] = guarded("prover_shaped", lambda: prover_shaped(pkg, bbg, srs, lg), 300)
         if "error" not in extra["prover_shaped"] and "cpu_baseline" in out and out["cpu_baseline"].get("kind") == "reference":
             # the reference binary stays on the MAIN thread: its OpenMP pippenger keeps per-thread state sized by the team it first saw,
@@ -606,7 +615,7 @@ def main():
     if extra["step_issue_floor"]:
         extra["step_issue_floor_ms"] = extra["step_issue_floor"]["ms"]
     # ---- the PCIe-inclusive drop-in entry points (host buffers in / out), one GPU
-    if rank == 0 and world == 1 and not args.no_sweeps and not stuck:
+    if rank == 0 and world == 1 and args.full and not args.no_sweeps and not stuck:
         extra["host_path"] = guarded("host_path", lambda: host_path(pkg, bbg, srs, lg), 120)
         rp = out.get("cpu_baseline", {}).get("real_prover", {})
         if "error" not in extra["host_path"] and "link_only_ms" in rp:  # the unmodified prover through the link-time shim (cpu_baseline.real_prover)
@@ -626,11 +635,12 @@ def main():
                 "proof_ms_this_run": hp.get("shim_linked_proof_ms"),
                 # ... and at BASELINE config 4's size as recorded on this hardware (2^20 gates takes a minute of circuit construction per run)
                 "proof_ms_2^20_gates_recorded": {"msm_fft_entry_points_wrapped_only": 1011.4, "construct_proof_wrapped_too": 27.23, "reference_cpu": 4802.6, "host_threads": 64,
-                                                  "source": "profiles/r04_real_prover.txt (same hardware, round 4; python bench.py --real-prover-log2 20 re-measures)"},
+                                                  "source": "profiles/r04_real_prover.txt (same hardware, round 4; python bench.py --full --real-prover-log2 20 re-measures)"},
                 "prover_shaped_resident_ms": (extra.get("prover_shaped") or {}).get("proof_ms"),
             }
-    # ---- BASELINE config 5: ONE 2^24 MSM + ONE 2^24 coset NTT over the N GPUs (strong scaling: total work fixed as N grows)
-    if not args.no_config5 and not stuck:
+    # ---- BASELINE config 5: ONE 2^24 MSM + ONE 2^24 coset NTT over the N GPUs (strong scaling: total work fixed as N grows); at N > 1 it is
+    # the headline and runs in every run, at N = 1 only with --full
+    if not args.no_config5 and not stuck and (world > 1 or args.full):
         srs.free()
         srs = None
         # timed_steps: the contract's K-step region on THIS workload too -- at N > 1 it becomes the line's headline (promote_config5 below),
@@ -638,14 +648,14 @@ def main():
         c5_side = (side, bbg_side) if dist is not None else None
         c5 = guarded("config5", lambda: config5(pkg, par, bbg, dist, dev, rank, world, args.config5_log2n, timed_steps=args.steps,
                                                 warmup=max(1, min(args.warmup, 3)), blocks=min(3, max(1, args.blocks)), side=c5_side,
-                                                dump_dir=args.dump_outputs if world > 1 else None), 600)
+                                                dump_dir=args.dump_outputs if world > 1 else None, legs=args.full), 600)
         if rank == 0:
             extra["config5"] = c5
             if isinstance(c5, dict) and "dump_outputs" in c5:
                 extra["dump_outputs"] = c5.pop("dump_outputs")
             promote_config5(out, c5, args, world, dist, one_device)
     # ---- BASELINE config 2 / 3 across sizes (isolated, one GPU)
-    if rank == 0 and world == 1 and not args.no_sweeps and not stuck:
+    if rank == 0 and world == 1 and args.full and not args.no_sweeps and not stuck:
         if srs is not None:
             srs.free()
             srs = None
@@ -830,11 +840,11 @@ def msm_sweep(pkg, bbg, dev, sizes=(16, 20, 22, 24)):
             "sizes": rows}
 
 
-def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, warmup=1, blocks=1, side=None, dump_dir=None):
+def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, warmup=1, blocks=1, side=None, dump_dir=None, legs=True):
     """BASELINE config 5 -- one 2^lg MSM (point-range shards, all-gather of the 96-byte partials + group sum) and one 2^lg coset NTT
     (residue-class shards, one all-to-all, size-N DFT) over the N ranks, inputs resident, STRONG scaling (total work fixed as N grows).
 
-    Two measurements: (i) the legs one at a time (max over ranks, best of `steps`): msm_ms / ntt_ms; (ii) with timed_steps = K > 0 the
+    Two measurements: (i) with legs, the legs one at a time (max over ranks, best of `steps`): msm_ms / ntt_ms; (ii) with timed_steps = K > 0 the
     contract's timed region on THIS workload: `warmup` untimed steps, then `blocks` blocks of exactly K steps (1 sharded MSM + 1 sharded
     coset NTT each) between two fences (pipeline flush + barrier + synchronize), max over ranks, median block -> `timed` (the N > 1
     headline of the line: value = 2^lg / seconds per step).  `side` = (stream, context): the exchange of earlier MSMs' partials runs there.
@@ -844,7 +854,9 @@ def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, w
     Self-checking: the inputs are the seeded ones of tests/golden/msm24.json (hashed SRS 0xBB254, synthetic_scalars(0xBB254 + 24))
     and tests/golden/ntt_large.json (synthetic_scalars(900 + lg), op coset_fft), both recorded from the compiled REFERENCE, so at
     lg = 24 rank 0 compares the group sum with the reference's 2^24 result and the SHA-256 of the gathered, canonicalised transform
-    with the reference's digest: `bit_exact_vs_reference`.  Only committed fixture DATA is read; nothing under oracle/ is used."""
+    with the reference's digest: `bit_exact_vs_reference`.  Only committed fixture DATA is read; nothing under oracle/ is used.
+    legs = False (a plain N > 1 run, where the timed region is the headline) leaves out (i) and the self-check: msm_ms / ntt_ms are absent
+    and both `bit_exact_vs_reference` entries None."""
     import hashlib
     import torch
     n = 1 << lg
@@ -924,7 +936,8 @@ def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, w
             ts.append(max_over_ranks(time.perf_counter() - t0))
         return min(ts)
 
-    t_msm, t_ntt = best(msm_step), best(ntt_step)
+    if legs:
+        t_msm, t_ntt = best(msm_step), best(ntt_step)
     # ---- the contract's timed region on this workload (N > 1: the line's headline)
     timed = None
     if timed_steps > 0:
@@ -967,25 +980,28 @@ def config5(pkg, par, bbg, dist, dev, rank, world, lg, steps=3, timed_steps=0, w
                 dumped = dump_outputs(dump_dir, pkg, bbg, tpipe.last_result(), nat)
     # ---- self-check against the reference's recorded results (after the timed regions; the legs are re-run on the recorded inputs)
     check = {"msm": None, "ntt": None, "source": "tests/golden/msm24.json, ntt_large.json, config5_small.json (compiled reference)"}
-    if timed is not None:
-        msm_step()
-        ntt_step()
-        fence()
-    if want_msm is not None:
-        jac = last["msm"].cpu().numpy().view(np.uint64).reshape(1, 12)
-        if rank == 0:
-            check["msm"] = bool(np.array_equal(bbg.g1_normalize(jac).reshape(-1), want_msm))
-    if want_ntt is not None:
-        nat = par.gather_natural_order(dist, last["ntt"], lg)  # rank g holds out[t*(m/G) + q] = A[(g*m/G + q) + m*t]  (parallel.ntt_sharded)
-        if rank == 0:
-            check["ntt"] = hashlib.sha256(pkg.fr_reduce_once(nat).tobytes()).hexdigest() == want_ntt
+    if legs:
+        if timed is not None:
+            msm_step()
+            ntt_step()
+            fence()
+        if want_msm is not None:
+            jac = last["msm"].cpu().numpy().view(np.uint64).reshape(1, 12)
+            if rank == 0:
+                check["msm"] = bool(np.array_equal(bbg.g1_normalize(jac).reshape(-1), want_msm))
+        if want_ntt is not None:
+            nat = par.gather_natural_order(dist, last["ntt"], lg)  # rank g holds out[t*(m/G) + q] = A[(g*m/G + q) + m*t]  (parallel.ntt_sharded)
+            if rank == 0:
+                check["ntt"] = hashlib.sha256(pkg.fr_reduce_once(nat).tobytes()).hexdigest() == want_ntt
     srs.free()
     res = {"workload": "ONE 2^%d-point MSM + ONE 2^%d coset NTT over %d GPU(s), strong scaling (north_star's split: point-range MSM shards + "
                        "all-gather of 96-B partials; residue-class NTT shards + one all-to-all)" % (lg, lg, world),
-           "n_gpus": world, "msm_ms": round(t_msm * 1e3, 3), "msm_mscalar_per_s": round(n / t_msm / 1e6, 2),
-           "ntt_ms": round(t_ntt * 1e3, 3), "ntt_gfield_ops_per_s": round(1.5 * n * lg / t_ntt / 1e9, 2),
-           "ntt_includes_input_restore_copy": True, "bit_exact_vs_reference": check,
+           "n_gpus": world, "bit_exact_vs_reference": check,
            "exchange": {"msm": "all_gather %d x 96 B" % world, "ntt": "all_to_all %.1f MiB per rank" % (32.0 * m * (world - 1) / world / 2**20)}}
+    if legs:
+        res.update({"msm_ms": round(t_msm * 1e3, 3), "msm_mscalar_per_s": round(n / t_msm / 1e6, 2),
+                    "ntt_ms": round(t_ntt * 1e3, 3), "ntt_gfield_ops_per_s": round(1.5 * n * lg / t_ntt / 1e9, 2),
+                    "ntt_includes_input_restore_copy": True})
     if timed is not None:
         res["timed"] = timed
         if dump_dir and rank == 0:

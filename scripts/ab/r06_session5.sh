@@ -3,7 +3,7 @@ python tests/tools/msm_window_sweep.py 8 15 8 13 2>&1 | grep -v amdgpu.ids | tee
 bash scripts/ab/small_msm_timeline.sh 12 k_tiny_recode 2>&1 | grep -v amdgpu.ids | head -9 | tee gpurun_out/r06_tiny_timeline_12.txt
 python tests/tools/r04_batch_ab.py 2>&1 | grep -v amdgpu.ids | head -12
 for lg in 10 12 14; do
-python bench.py --log2n $lg --steps 10 --warmup 2 --blocks 1 --no-cpu-baseline --no-config5 --no-sweeps 2>/dev/null | tail -1 | python -c "
+python bench.py --full --log2n $lg --steps 10 --warmup 2 --blocks 1 --no-cpu-baseline --no-config5 --no-sweeps 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('prover_shaped 2^$lg', d['extra']['prover_shaped'].get('proof_ms'), 'step ms', d['ms_per_step'])"
 done

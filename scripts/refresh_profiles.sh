@@ -89,10 +89,10 @@ $LEGS > /tmp/c5_ctl.log 2>&1
   python $ROOT/scripts/rocpd_summary.py pmc $C5DBS
 } > $OUT/${ROUND}_config5_legs_$TAG.txt
 # ---- pass 7: the resident prover rounds
-rm -rf /tmp/prof_ps && rocprofv3 --kernel-trace -d /tmp/prof_ps -o bench -- python $ROOT/bench.py --steps 2 --warmup 1 --blocks 1 --no-cpu-baseline --no-config5 --no-sweeps > /tmp/bench_ps.log 2>&1
+rm -rf /tmp/prof_ps && rocprofv3 --kernel-trace -d /tmp/prof_ps -o bench -- python $ROOT/bench.py --full --steps 2 --warmup 1 --blocks 1 --no-cpu-baseline --no-config5 --no-sweeps > /tmp/bench_ps.log 2>&1
 {
   stamp
-  echo "# rocprofv3 --kernel-trace -- python bench.py --steps 2 --warmup 1 --blocks 1 --no-cpu-baseline --no-config5"
+  echo "# rocprofv3 --kernel-trace -- python bench.py --full --steps 2 --warmup 1 --blocks 1 --no-cpu-baseline --no-config5 --no-sweeps"
   echo "# dominated by extra.prover_shaped: 6 passes of the TurboPLONK prover sequence at n = 2^20 on the resident prover rounds (bbg_prover_*)"
   grep "^{\"metric\"" /tmp/bench_ps.log | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('# prover_shaped:', json.dumps(d['extra']['prover_shaped']))"
   echo

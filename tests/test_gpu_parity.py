@@ -1285,6 +1285,55 @@ def _dumped_u64(a):
     return h[:, 0] | (h[:, 1] << np.uint64(32))
 
 
+def _bench_dump(dump_dir, out):
+    """The three arrays bench.py --dump-outputs wrote, as the line lists them: float64 halves of u64 limbs."""
+    dump = {k: np.load(dump_dir / (k + ".npy")) for k in ("msm_affine", "ntt_index", "ntt_values")}
+    assert out["extra"]["dump_outputs"]["files"] == {k + ".npy": list(a.shape) for k, a in dump.items()}
+    assert all(a.dtype == np.float64 for a in dump.values())
+    return dump
+
+
+def _check_step_dump(dump_dir, out, pkg, oracle, lg, warmup):
+    """--dump-outputs of an N = 1 line: the last step's MSM point is the one the CPU oracle computes and its NTT output is the oracle's
+    transform applied once per warm-up and timed step (inputs as bench.py seeds them)."""
+    dump = _bench_dump(dump_dir, out)
+    n = 1 << lg
+    assert dump["msm_affine"].shape == (16,) and dump["ntt_values"].shape == (n, 8)
+    assert np.array_equal(dump["ntt_index"], np.arange(n))
+    want = oracle.pippenger(pkg.synthetic_scalars(0xBB254 + 3, n), oracle.srs_hashed(0xBB254, n))
+    assert np.array_equal(_dumped_u64(dump["msm_affine"]), want)
+    want = pkg.synthetic_scalars(0xBB254 + 100 + lg, n)  # bench.py's coefficients: one forward NTT in place per step
+    for _ in range(warmup + out["timed_steps"]):
+        want = oracle.ntt(want, 0)
+    assert np.array_equal(_dumped_u64(dump["ntt_values"]).reshape(-1, 4), want)
+
+
+def _check_config5_dump(dump_dir, out, pkg, oracle, lg, world, warmup):
+    """--dump-outputs of an N > 1 line: config 5's last timed step (the headline) -- the MSM the reference recorded, and the whole 2^lg
+    transform."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = _bench_dump(dump_dir, out)
+    rec = [r for r in json.load(open(os.path.join(root, "tests", "golden", "config5_small.json")))["sizes"] if r["log2n"] == lg][0]
+    assert np.array_equal(_dumped_u64(dump["msm_affine"]), np.frombuffer(bytes.fromhex(rec["msm_result"]), dtype=np.uint64))
+    n, G = 1 << lg, world
+    m = n // G
+    assert np.array_equal(dump["ntt_index"], np.arange(n))
+    # `warmup` + the timed steps, each a sharded coset_fft of what rank g's buffer holds (parallel.ntt_sharded): its residue class a[g + G j]
+    # in, and after the step the local transform Z_g[q] = sum_j a[g + G j] c^(g + G j) w_n^((g + G j) q), q < m -- residue class g's share
+    # of the coset transform, i.e. the coset_fft of a with every other class zeroed, at its first m points.  The last step's output (the
+    # whole transform of its input, gathered in natural order) is what is dumped.
+    a = pkg.synthetic_scalars(900 + lg, n)
+    for _ in range(warmup + out["timed_steps"] - 1):
+        nxt = np.empty_like(a)
+        for g in range(G):
+            b = np.zeros_like(a)
+            b[g::G] = a[g::G]
+            nxt[g::G] = oracle.ntt(b, 2)[:m]
+        a = nxt
+    A = oracle.ntt(a, 2)
+    assert np.array_equal(_dumped_u64(dump["ntt_values"]).reshape(-1, 4), A)
+
+
 def test_bench_contract_and_dist_path(tmp_path):
     """bench.py prints one JSON line with the contract's fields; BBG_FORCE_DIST=1 drives the RCCL all-gather +
     software-pipelined sharded-MSM path (world of 1) and the result must still be bit-exact against the CPU reference.
@@ -1299,7 +1348,7 @@ def test_bench_contract_and_dist_path(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BBG_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     env.pop("MASTER_PORT", None)  # bench.py picks a free port for its world of one: two suites on one box cannot collide
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--log2n", "16", "--config5-log2n", "18",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--log2n", "16", "--config5-log2n", "18",
                         "--real-prover-log2", "10", "--dump-outputs", str(tmp_path / "dump")], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -1323,21 +1372,8 @@ def test_bench_contract_and_dist_path(tmp_path):
     if rp is not None and "error" not in rp:  # oracle/_ref prover libraries shipped: the real reference prover, CPU vs link-time shim
         assert rp["byte_identical_to_cpu_proof"] is True and rp["verified"] == [1, 1, 1, 1] and rp["wrapped_zero_edits_ms"] < rp["link_only_ms"]
         assert out["extra"]["host_path"]["shim_linked_proof_ms"]["construct_proof_wrapped_too"] == rp["wrapped_zero_edits_ms"]
-    # the dumped outputs: float64 halves of u64 limbs; the affine point is the MSM the CPU reference checked (inputs as bench.py seeds them)
-    dump = {k: np.load(tmp_path / "dump" / (k + ".npy")) for k in ("msm_affine", "ntt_index", "ntt_values")}
-    assert out["extra"]["dump_outputs"]["files"] == {k + ".npy": list(a.shape) for k, a in dump.items()}
-    assert all(a.dtype == np.float64 for a in dump.values())
-    assert dump["msm_affine"].shape == (16,) and dump["ntt_values"].shape == (1 << 16, 8)
-    assert np.array_equal(dump["ntt_index"], np.arange(1 << 16))
-    oracle = Oracle()
-    pkg = ge.load_package()
-    n = 1 << 16
-    want = oracle.pippenger(pkg.synthetic_scalars(0xBB254 + 3, n), oracle.srs_hashed(0xBB254, n))
-    assert np.array_equal(_dumped_u64(dump["msm_affine"]), want)
-    want = pkg.synthetic_scalars(0xBB254 + 100 + 16, n)  # bench.py's coefficients: one forward NTT in place per step, 1 warm-up + 15 timed
-    for _ in range(1 + out["timed_steps"]):
-        want = oracle.ntt(want, 0)
-    assert np.array_equal(_dumped_u64(dump["ntt_values"]).reshape(-1, 4), want)
+    # the dumped outputs: the affine point is the MSM the CPU reference checked; the NTT output after 1 warm-up + 15 timed steps
+    _check_step_dump(tmp_path / "dump", out, ge.load_package(), Oracle(), 16, 1)
 
 
 # at most 6 processes may hold a GPU open at once on a shared machine: this suite's own process (the session context) + 4 ranks stays
@@ -1358,7 +1394,7 @@ def test_bench_self_launched_ranks_one_device_rehearsal(world, tmp_path, pkg, or
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "BBG_FORCE_DIST")}
     env.update(BBG_DIST_ONE_DEVICE="1", BBG_BENCH_LAUNCH_TIMEOUT="800")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--blocks", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--full", "--steps", "6", "--warmup", "2", "--blocks", "2",
                         "--log2n", "14", "--config5-log2n", "16", "--dump-outputs", str(tmp_path / "dump")], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -1383,28 +1419,52 @@ def test_bench_self_launched_ranks_one_device_rehearsal(world, tmp_path, pkg, or
     assert c5["bit_exact_vs_reference"]["msm"] is True and c5["bit_exact_vs_reference"]["ntt"] is True, c5
     assert c5["exchange"]["msm"] == "all_gather %d x 96 B" % world and not c5["exchange"]["ntt"].startswith("all_to_all 0.0"), c5
     assert "cpu_baseline" not in out  # rank 0 runs the CPU leg at N = 1 only
-    # N > 1: --dump-outputs writes config 5's last timed step (the headline): the MSM the reference recorded, and the whole 2^16 transform
-    dump = {k: np.load(tmp_path / "dump" / (k + ".npy")) for k in ("msm_affine", "ntt_index", "ntt_values")}
-    assert out["extra"]["dump_outputs"]["files"] == {k + ".npy": list(a.shape) for k, a in dump.items()}
-    rec = [r for r in json.load(open(os.path.join(root, "tests", "golden", "config5_small.json")))["sizes"] if r["log2n"] == 16][0]
-    assert np.array_equal(_dumped_u64(dump["msm_affine"]), np.frombuffer(bytes.fromhex(rec["msm_result"]), dtype=np.uint64))
-    n, G = 1 << 16, world
-    m = n // G
-    assert np.array_equal(dump["ntt_index"], np.arange(n))
-    # 2 warm-up + 12 timed steps, each a sharded coset_fft of what rank g's buffer holds (parallel.ntt_sharded): its residue class a[g + G j]
-    # in, and after the step the local transform Z_g[q] = sum_j a[g + G j] c^(g + G j) w_n^((g + G j) q), q < m -- residue class g's share
-    # of the coset transform, i.e. the coset_fft of a with every other class zeroed, at its first m points.  The last step's output (the
-    # whole transform of its input, gathered in natural order) is what is dumped.
-    a = pkg.synthetic_scalars(900 + 16, n)
-    for _ in range(2 + out["timed_steps"] - 1):
-        nxt = np.empty_like(a)
-        for g in range(G):
-            b = np.zeros_like(a)
-            b[g::G] = a[g::G]
-            nxt[g::G] = oracle.ntt(b, 2)[:m]
-        a = nxt
-    A = oracle.ntt(a, 2)
-    assert np.array_equal(_dumped_u64(dump["ntt_values"]).reshape(-1, 4), A)
+    # N > 1: --dump-outputs writes config 5's last timed step (the headline), after 2 warm-up + 12 timed steps
+    _check_config5_dump(tmp_path / "dump", out, pkg, oracle, 16, world, 2)
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_is_the_headline_alone(world, tmp_path, pkg, oracle):
+    """`python bench.py` without --full: set-up, warm-up, the timed blocks and --dump-outputs, nothing that takes runs of its own.  At N = 1
+    (no launcher, no process group: the run every change is measured with) the line has the contract's fields and none of the CPU baseline,
+    config 5, the prover-shaped sequence, the host-buffer entry points or the sweeps.  At N > 1 (the one-device rehearsal) config 5's timed
+    region is still the headline, without its separately timed legs and its reference check.  Either way the dumped outputs are checked as
+    in the --full tests above."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "BBG_FORCE_DIST")}
+    if world == 1:
+        argv = ["--steps", "3", "--warmup", "1", "--log2n", "16"]
+    else:
+        env.update(BBG_DIST_ONE_DEVICE="1", BBG_BENCH_LAUNCH_TIMEOUT="800")
+        argv = ["--gpus", str(world), "--steps", "6", "--warmup", "2", "--blocks", "2", "--log2n", "14", "--config5-log2n", "16"]
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv + ["--dump-outputs", str(tmp_path / "dump")], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, lines, r.stderr.decode()[-3000:])
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "timed_steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "roofline"):
+        assert key in out, key
+    assert "error" not in out and out["n_gpus"] == world and out["value"] > 0 and out["ms_per_step"] > 0, out
+    assert "cpu_baseline" not in out
+    assert not {"prover_shaped", "host_path", "dropin", "ntt_sweep", "msm_sweep"} & set(out["extra"]), sorted(out["extra"])
+    if world == 1:
+        assert out["scaling"] == "weak" and "strong_scaling" not in out and "config5" not in out["extra"]
+        assert out["steps"] == 3 and out["timed_steps"] == 3 * 5 and len(out["extra"]["timed_blocks_ms"]) == 5
+        assert abs(out["ms_per_step"] * 3 - sorted(out["extra"]["timed_blocks_ms"])[2]) < 1e-2
+        assert abs(out["value"] - (1 << 16) / (out["ms_per_step"] * 1e-3) / 1e6) < 0.01 * out["value"]
+        assert out["roofline"]["frac"] > 0 and "profile_stamp" in out["extra"]
+        _check_step_dump(tmp_path / "dump", out, pkg, oracle, 16, 1)
+    else:
+        assert out["scaling"] == "strong" and "config 5" in out["metric"] and out["config"]["log2n"] == 16, out
+        c5 = out["extra"]["config5"]
+        assert len(c5["timed"]["blocks_ms"]) == 2 and c5["timed"]["steps"] == 6 and out["timed_steps"] == 6 * 2
+        assert out["value"] == out["strong_scaling"]["value"] == c5["timed"]["value_mscalar_per_s"]
+        assert "msm_ms" not in c5 and "ntt_ms" not in c5
+        assert c5["bit_exact_vs_reference"]["msm"] is None and c5["bit_exact_vs_reference"]["ntt"] is None
+        _check_config5_dump(tmp_path / "dump", out, pkg, oracle, 16, world, 2)
 
 
 @pytest.mark.parametrize("lg", [25, 26, 27, 28])
