@@ -10,6 +10,7 @@ import pytest
 
 from conftest import limbs, sha, unhex
 import callback_engines  # tests/tools: Python stand-ins for work-queue callbacks (test tooling)
+from msm_options import msm_options  # tests/tools: MSM options set for a block, library defaults restored
 
 pytestmark = pytest.mark.gpu
 
@@ -484,22 +485,16 @@ def test_msm_option_matrix_is_bit_identical(pkg, oracle, bbg, srs16):
     issued, never the point: every combination against the oracle, at sizes on both sides of the lane-group combine."""
     srs = srs16
     pts = srs.read(0, 1 << 16)
-    try:
-        for n in (1, 257, 4096, 1 << 16):
-            sc = pkg.synthetic_scalars(4242 + n, n)
-            want = oracle.pippenger(sc, pts[:n])
-            for quad in (0, 15, 5, 10):
-                for pieces in (1, 4):
-                    for overlap in (0, 1):
-                        bbg.set_option("msm_reduce_quad", quad)
-                        bbg.set_option("msm_upload_pieces", pieces)
-                        bbg.set_option("msm_async_reduce", overlap)
+    for n in (1, 257, 4096, 1 << 16):
+        sc = pkg.synthetic_scalars(4242 + n, n)
+        want = oracle.pippenger(sc, pts[:n])
+        for quad in (0, 15, 14, 5, 10):
+            for pieces in (1, 4):
+                for overlap in (0, 1):
+                    # every MSM option back at its library default afterwards (msm_reduce_quad: 14, not 15)
+                    with msm_options(bbg, msm_reduce_quad=quad, msm_upload_pieces=pieces, msm_async_reduce=overlap):
                         got = oracle.jac_to_affine(bbg.msm(srs, sc))
-                        assert np.array_equal(got, want), (n, quad, pieces, overlap)
-    finally:
-        bbg.set_option("msm_reduce_quad", 15)
-        bbg.set_option("msm_upload_pieces", 1)
-        bbg.set_option("msm_async_reduce", 0)
+                    assert np.array_equal(got, want), (n, quad, pieces, overlap)
 
 
 def test_msm_limbs29_degenerate_runs(pkg, oracle, bbg, srs16):
