@@ -69,6 +69,7 @@ def load_library():
         "bbg_srs_read": (cint, [vp, sz, sz, vp]),
         "bbg_srs_free": (None, [vp]),
         "bbg_srs_retain": (cint, [vp]),
+        "bbg_srs_lagrange": (cint, [vp, vp, ctypes.c_uint, ctypes.POINTER(vp)]),
         "bbg_msm": (cint, [vp, vp, vp, sz, sz, vp]),
         "bbg_msm_device": (cint, [vp, vp, vp, sz, sz, vp]),
         "bbg_msm_batch": (cint, [vp, vp, sz, vp, vp, vp, vp]),
@@ -145,7 +146,7 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "bbg_device_count", "bbg_init", "bbg_destroy", "bbg_last_error", "bbg_sync", "bbg_join", "bbg_join_lag", "bbg_set_stream", "bbg_srs_register",
     "bbg_srs_register_device", "bbg_srs_synth_linear", "bbg_srs_synth_hashed", "bbg_srs_load_transcript", "bbg_srs_num_points", "bbg_srs_read",
-    "bbg_srs_free", "bbg_srs_retain", "bbg_msm", "bbg_msm_device", "bbg_msm_batch", "bbg_msm_batch_device", "bbg_msm_plan", "bbg_ntt_plan", "bbg_memory_report",
+    "bbg_srs_free", "bbg_srs_retain", "bbg_srs_lagrange", "bbg_msm", "bbg_msm_device", "bbg_msm_batch", "bbg_msm_batch_device", "bbg_msm_plan", "bbg_ntt_plan", "bbg_memory_report",
     "bbg_memory_trim", "bbg_prover_device_bytes", "bbg_g1_sum", "bbg_g1_sum_device", "bbg_g1_normalize", "bbg_ntt", "bbg_ntt_device", "bbg_coset_fft_extend", "bbg_quotient_widget_device", "bbg_poly_linear_combination_device", "bbg_permutation_grand_product_device", "bbg_poly_evaluate", "bbg_kate_opening",
     "bbg_divide_by_pseudo_vanishing",
     "bbg_ntt_prepare", "bbg_coset_fft_split", "bbg_coset_fft_split_device", "bbg_scale_powers_device", "bbg_fr_root_pow", "bbg_fr_pow", "bbg_cross_dft_device", "bbg_poly_op_device", "bbg_poly_evaluate_device", "bbg_kate_opening_device",
@@ -193,6 +194,12 @@ class Srs:
         """Ignition-format files directory/transcriptNN.dat holding points 1 .. n-1 (bbg_srs_write_transcript)."""
         g2 = None if g2_x_raw is None else ctypes.create_string_buffer(bytes(g2_x_raw), 128)
         self._owner._ck(self._owner.lib.bbg_srs_write_transcript(self.handle, str(directory).encode(), points_per_file, g2))
+
+    def lagrange(self, log2n):
+        """The Lagrange-base form of the first 2^log2n points, LB[k] = n^-1 sum_j w_n^(-jk) M_j, as an Srs of its own (bbg_srs_lagrange)."""
+        h = ctypes.c_void_p()
+        self._owner._ck(self._owner.lib.bbg_srs_lagrange(self._owner.ctx, self.handle, log2n, ctypes.byref(h)))
+        return Srs(self._owner, h)
 
     def free(self):
         if self.handle:

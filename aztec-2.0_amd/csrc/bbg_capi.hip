@@ -782,6 +782,53 @@ int bbg_srs_read(bbg_srs* srs, size_t from, size_t count, uint64_t* out_points)
     return BBG_OK;
 }
 
+// lagrange_base::transform_srs (srs/lagrange_base_transformation/lagrange_base.cpp:31-46) on the device (ecntt.hip): the first
+// 2^log2n points of `srs` become LB[k] = n^-1 sum_j w_n^(-jk) M_j, registered as an SRS of its own.  Everything is queued on the
+// context's stream; the one host synchronisation is the table build's (make_srs), after which the infinity flag is read.
+int bbg_srs_lagrange(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, bbg_srs** out)
+{
+    CHECK_CTX(ctx);
+    if (!srs || !out) { set_error("bbg_srs_lagrange: null argument"); return BBG_E_INVALID; }
+    if (log2n < 1 || log2n > 28) { set_error("bbg_srs_lagrange: log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    const size_t n = (size_t)1 << log2n;
+    if (n > srs->s.n) { set_error("bbg_srs_lagrange: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
+    if (srs->s.device != ctx->device) { set_error("bbg_srs_lagrange: the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    void *d_work = nullptr, *d_plain = nullptr;
+    unsigned* d_flag = nullptr;
+    unsigned* h_flag = nullptr; // pinned: the copy behind the kernels stays asynchronous
+    bbg_srs* res = nullptr;
+    int rc = BBG_OK;
+    hipError_t e = hipMalloc(&d_work, n * 128);
+    if (e == hipSuccess) e = hipMalloc(&d_plain, n * 64);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_flag, sizeof(unsigned));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h_flag, sizeof(unsigned), hipHostMallocDefault);
+    if (e == hipSuccess) {
+        *h_flag = 1; // stays set unless the copy below has run
+        e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), ctx->stream);
+    }
+    if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_lagrange: working set", __FILE__, __LINE__);
+    if (rc == BBG_OK) rc = ecntt_run(ctx, srs->s.points, log2n, d_work, d_plain, d_flag, ctx->stream);
+    if (rc == BBG_OK) {
+        e = hipMemcpyAsync(h_flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_lagrange: flag copy", __FILE__, __LINE__);
+    }
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
+    const bool inf = rc == BBG_OK && *h_flag != 0;
+    if (d_work) (void)hipFree(d_work);
+    if (d_plain) (void)hipFree(d_plain);
+    if (d_flag) (void)hipFree(d_flag);
+    if (h_flag) (void)hipHostFree(h_flag);
+    if (rc) return rc;
+    if (inf) {
+        bbg_srs_free(res);
+        set_error("bbg_srs_lagrange: the transform has a point at infinity among its outputs (linearly dependent input points); an SRS cannot hold one");
+        return BBG_E_INFINITY;
+    }
+    *out = res;
+    return BBG_OK;
+}
+
 int bbg_srs_retain(bbg_srs* srs)
 {
     if (!srs) { set_error("bbg_srs_retain: null handle"); return BBG_E_INVALID; }

@@ -222,4 +222,8 @@ int srs_synth_linear(bbg_ctx* ctx, uint64_t a, uint64_t s, size_t n, void* d_poi
 int msm_join(bbg_ctx* ctx, hipStream_t stream);
 int srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, void* d_points, hipStream_t stream);
 int g1_sum_device(bbg_ctx* ctx, const void* d_jacs, size_t n, void* d_out, hipStream_t stream);
+// ecntt.hip: the inverse NTT over G1 behind bbg_srs_lagrange.  d_src: 2^log2n plain affine points (read only); d_work: 2^log2n x 128 B;
+// d_out: 2^log2n x 64 B canonical affine; *d_inf_flag (cleared by the caller on `stream`) is set when an output is the point at infinity.
+// Queues only, no host synchronisation.
+int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
 } // namespace bbg

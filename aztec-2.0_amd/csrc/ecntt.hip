@@ -1,0 +1,161 @@
+// Lagrange-base transform of a reference string for gfx950: an inverse NTT whose elements are BN254 G1 points.
+//
+// Computes what lagrange_base::transform_srs computes (reference srs/lagrange_base_transformation/lagrange_base.cpp:6-46): for
+// n = 2^log2n and the monomial points M_0 .. M_{n-1}
+//
+//     LB[k] = n^-1 * sum_j w_n^(-j k) * M_j        k = 0 .. n-1, natural order, affine
+//
+// with w_n = fr::get_root_of_unity(log2n), so that LB[k] = [L_k(x)] G when M_j = [x^j] G.  (The reference's recursive g1fft starts its
+// running twiddle at `root`, not 1: its result[i] is the value at root^(i+1), and transform_srs rotates the indices by one to get
+// back to natural order, :41-45.)
+//
+// The reference recurses on one thread and does n/2 log2 n + n full scalar multiplications.  Here:
+//   * k_ecntt_load     copies the source points, bit-reversed, into a working set of n XYZZ points (128 B each) the call owns;
+//   * k_ecntt_stage    one launch per radix-2 stage of a decimation-in-time schedule, one butterfly per thread, in place:
+//                      t = w B, A' = A + t, B' = A - t.  w = w_n^(-j n/2m) is rebuilt from the domain's table of root_inv^(2^b)
+//                      (at most log2 n Fr products beside 254 doublings), taken out of Montgomery form and used as a plain 254-bit
+//                      integer by a left-to-right double-and-add on the complete XYZZ formulas of curve.hip.h.  Butterflies whose
+//                      twiddle is 1 skip the multiplication (all of stage 0).  The LAST stage carries n^-1: its twiddles are n^-1 w
+//                      and its A operands are multiplied by n^-1 (n/2 extra scalar multiplications, 1 / log2 n of the work, and no
+//                      pass of its own);
+//   * k_ecntt_normalize  batched conversion to canonical affine, one inversion per NORM_CH points; a point at infinity among the
+//                      outputs raises a flag (an SRS handle never holds one) and the call fails.
+// All group-law cases (equal / opposite operands, infinities inside the transform) are handled by xyzz_add / xyzz_dbl.
+#include "bbg_internal.h"
+#include "curve.hip.h"
+#include "ntt_consts.hip.h"
+
+namespace bbg {
+
+static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
+
+__device__ __forceinline__ Xyzz xyzz_neg(const Xyzz& p)
+{
+    Xyzz r = p;
+    r.y = fe_neg(p.y);
+    return r;
+}
+
+// k * P for a plain (non-Montgomery) canonical k < r < 2^254: left-to-right double-and-add.  The scalar is shifted left one bit per
+// step so that the bit under test is always bit 255: no runtime-indexed limb, and the loop body exists once.
+__device__ __forceinline__ Xyzz xyzz_mul_fr(const Xyzz& p, Fr k)
+{
+    Xyzz acc = xyzz_inf();
+    for (int i = 0; i < 256; i++) {
+        const bool bit = (k.v[7] >> 31) != 0;
+#pragma unroll
+        for (int l = 7; l > 0; l--) k.v[l] = (k.v[l] << 1) | (k.v[l - 1] >> 31);
+        k.v[0] <<= 1;
+        acc = xyzz_dbl(acc); // returns at once while acc is still infinity
+        if (bit) acc = xyzz_add(acc, p);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ size_t bit_reverse(size_t i, unsigned bits)
+{
+    return (size_t)(__brevll((unsigned long long)i) >> (64 - bits));
+}
+
+// work[i] = M[bitrev(i)] in XYZZ form (the input permutation of the decimation-in-time schedule)
+__global__ void __launch_bounds__(256) k_ecntt_load(const Affine* __restrict__ src, Xyzz* __restrict__ work, unsigned log2n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ((size_t)1 << log2n)) return;
+    const Affine a = aff_load(src + bit_reverse(i, log2n));
+    xyzz_store(work + i, aff_is_inf(a) ? xyzz_inf() : xyzz_from_affine(a));
+}
+
+// stage s (half-size m = 2^s) of the transform, in place; thread t owns the butterfly (i, i + m), i = (t / m) 2m + t % m.
+// Two waves per SIMD: 246 VGPRs, no scratch, no LDS; three would cap the kernel at 168 VGPRs and spill inside the multiplication loop
+// (A/B: make EXTRA=-DBBG_ECNTT_OCC=3).
+#ifndef BBG_ECNTT_OCC
+#define BBG_ECNTT_OCC 2
+#endif
+__global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ((size_t)1 << (log2n - 1))) return;
+    const size_t m = (size_t)1 << s;
+    const size_t j = t & (m - 1);
+    const size_t i = ((t >> s) << (s + 1)) + j;
+    Xyzz b = xyzz_load(work + i + m);
+    if (last || j != 0) {
+        Fr w = pow_from_table(dc->pow2_root_inv, (uint64_t)j << (log2n - 1 - s)); // w_2m^-j = w_n^(-j n / 2m)
+        if (last) w = fe_mul(w, dc->n_inv);
+        b = xyzz_mul_fr(b, fe_reduce_once(fe_from_mont(w)));
+    }
+    Xyzz a = xyzz_load(work + i);
+    if (last) a = xyzz_mul_fr(a, fe_reduce_once(fe_from_mont(dc->n_inv)));
+    xyzz_store(work + i, xyzz_add(a, b));
+    xyzz_store(work + i + m, xyzz_add(a, xyzz_neg(b)));
+}
+
+// XYZZ -> canonical affine, NORM_CH consecutive points per thread behind one inversion (as k_srs_synth does).  A point at infinity is
+// reported through *inf_flag and stored as the generator, so that whatever is queued behind this kernel still reads valid points; the
+// host discards the result.
+constexpr int NORM_CH = 8;
+__global__ void __launch_bounds__(128) k_ecntt_normalize(const Xyzz* __restrict__ work, Affine* __restrict__ out, size_t n, unsigned* inf_flag)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i0 = t * NORM_CH;
+    if (i0 >= n) return;
+    Fq prod[NORM_CH];
+    Fq acc = Fq::one();
+    int cnt = 0;
+    bool any_inf = false;
+    for (int e = 0; e < NORM_CH && i0 + e < n; e++) {
+        const Fq zz = fe_load<FqP>(&work[i0 + e].zz), zzz = fe_load<FqP>(&work[i0 + e].zzz);
+        prod[e] = acc;
+        if (zz.is_zero_raw())
+            any_inf = true;
+        else
+            acc = fe_mul(acc, fe_mul(zz, zzz));
+        cnt++;
+    }
+    Fq inv = fq_invert(acc);
+    for (int e = cnt - 1; e >= 0; e--) {
+        const Xyzz p = xyzz_load(work + i0 + e);
+        Affine o;
+        if (xyzz_is_inf(p)) {
+            o.x = Fq::one();
+            Fq two = Fq::zero();
+            two.v[0] = 2;
+            o.y = fe_reduce_once(fe_to_mont(two));
+        } else {
+            const Fq iz = fe_mul(inv, prod[e]);
+            inv = fe_mul(inv, fe_mul(p.zz, p.zzz));
+            o.x = fe_reduce_once(fe_mul(p.x, fe_mul(iz, p.zzz)));
+            o.y = fe_reduce_once(fe_mul(p.y, fe_mul(iz, p.zz)));
+        }
+        aff_store(out + i0 + e, o);
+    }
+    if (any_inf) atomicOr(inf_flag, 1u);
+}
+
+// Queues the whole transform on `st`: d_src = 2^log2n plain affine points (read only), d_work = 2^log2n x 128 B, d_out = 2^log2n x 64 B,
+// d_inf_flag = one word the caller has cleared on `st`.  No host synchronisation.
+int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t st)
+{
+    if (log2n < 1 || log2n > 28) { set_error("ecntt: log2n out of range (1 .. 28)"); return BBG_E_INVALID; }
+    void* consts = nullptr;
+    int rc = ntt_domain_consts(ctx, log2n, &consts); // root_inv^(2^b) and n^-1 of the scalar NTT's domain
+    if (rc) return rc;
+    const size_t n = (size_t)1 << log2n;
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        hipLaunchKernelGGL(k_ecntt_load, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Affine*)d_src, (Xyzz*)d_work, log2n);
+        for (unsigned s = 0; s < log2n; s++)
+            hipLaunchKernelGGL(k_ecntt_stage, dim3(grid_for(n / 2, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s,
+                               s + 1 == log2n ? 1 : 0);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_normalize", st);
+        hipLaunchKernelGGL(k_ecntt_normalize, dim3(grid_for((n + NORM_CH - 1) / NORM_CH, 128)), dim3(128), 0, st, (const Xyzz*)d_work, (Affine*)d_out, n,
+                           d_inf_flag);
+    }
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+} // namespace bbg

@@ -33,6 +33,7 @@ extern "C" {
 #define BBG_E_HIP (-2)      /* a HIP runtime call failed; see bbg_last_error() */
 #define BBG_E_NODEVICE (-3) /* no gfx950 device visible */
 #define BBG_E_NOMEM (-4)
+#define BBG_E_INFINITY (-5) /* a result that must be a finite point is the point at infinity (bbg_srs_lagrange) */
 
 typedef struct bbg_ctx bbg_ctx; /* one per GPU / per process rank */
 typedef struct bbg_srs bbg_srs; /* device-resident SRS (the Pippenger point table) */
@@ -89,6 +90,14 @@ int bbg_transcript_checksum(const void* data, size_t len, uint8_t out[64]);
 size_t bbg_srs_num_points(const bbg_srs* srs);
 /* Copies points [from, from+count) back to the host (64-byte Montgomery affine each). */
 int bbg_srs_read(bbg_srs* srs, size_t from, size_t count, uint64_t* out_points);
+/* The Lagrange-base form of a reference string: lagrange_base::transform_srs (srs/lagrange_base_transformation/lagrange_base.cpp:31-46)
+ * as an inverse NTT over G1 on the device.  With n = 2^log2n (1 <= log2n <= 28, n <= bbg_srs_num_points(srs)) and M_j the first n points of `srs`,
+ * *out is a new SRS of n points LB[k] = n^-1 * sum_j w_n^(-j k) M_j (w_n = fr::get_root_of_unity(log2n), natural order): for a monomial string
+ * M_j = [x^j] G that is [L_k(x)] G, so bbg_msm over a polynomial's EVALUATIONS and *out equals bbg_msm over its coefficients and `srs`.
+ * `srs` is only read and must live on the context's device; *out has its own lifetime and is an ordinary SRS for every entry point.
+ * Points at infinity inside the transform are handled; one among the OUTPUTS (linearly dependent inputs) fails with BBG_E_INFINITY and
+ * leaves *out untouched.  Timed under "ecntt_stages" / "ecntt_normalize" (bbg_profile_get). */
+int bbg_srs_lagrange(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, bbg_srs** out);
 /* Shared ownership: bbg_srs_retain adds an owner, bbg_srs_free drops one; the device memory goes with the last owner.  bbg_prover_create
  * retains the SRS it is given (and bbg_prover_destroy releases it), so freeing or replacing a cached SRS never invalidates a live prover. */
 int bbg_srs_retain(bbg_srs* srs);
@@ -396,7 +405,7 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
  * Every value of every option gives bit-identical results; they exist for A/B measurements. */
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
- * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget".  enable(…, 1) clears previous samples. */
+ * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.

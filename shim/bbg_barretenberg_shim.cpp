@@ -8,6 +8,7 @@
 //   barretenberg::polynomial_arithmetic::fft / ifft / coset_fft (x2) / coset_ifft / fft_with_constant /
 //       coset_fft_with_constant / coset_fft_with_generator_shift / ifft_with_constant
 //                                                                            (polynomial_arithmetic.hpp:23-39)
+//   barretenberg::lagrange_base::transform_srs          (srs/lagrange_base_transformation/lagrange_base.hpp:11-14)
 //
 // forwarding to libbbg.so's C ABI (include/bbg.h).  Two ways to put it in front of the stock prover WITHOUT editing
 // a single reference file:
@@ -436,6 +437,10 @@ fr compute_kate_opening_coefficients(const fr* src, fr* dest, const fr& z, const
 void divide_by_pseudo_vanishing_polynomial(fr* coeffs, const evaluation_domain& src_domain, const evaluation_domain& target_domain,
                                            const size_t num_roots_cut_out_of_vanishing_polynomial)
     SHIM_NAME("_ZN12barretenberg21polynomial_arithmetic37divide_by_pseudo_vanishing_polynomialEPNS_5fieldINS_13Bn254FrParamsEEERKNS_17evaluation_domainES7_m");
+// the Lagrange-base form of a reference string (srs/lagrange_base_transformation/lagrange_base.hpp:13); `monomials` is the PLAIN table
+// (stride 64 bytes), not Pippenger's interleaved one
+void transform_srs(g1::affine_element* monomials, g1::affine_element* lagrange_base_affine, const size_t degree)
+    SHIM_NAME("_ZN12barretenberg13lagrange_base13transform_srsEPNS_14group_elements14affine_elementINS_5fieldINS_13Bn254FqParamsEEENS3_INS_13Bn254FrParamsEEENS_13Bn254G1ParamsEEESA_m");
 
 g1::element pippenger(fr* scalars, g1::affine_element* points, const size_t num_points, pippenger_runtime_state&, bool)
 {
@@ -490,5 +495,19 @@ void divide_by_pseudo_vanishing_polynomial(fr* coeffs, const evaluation_domain& 
     if (bbg_divide_by_pseudo_vanishing(context(), reinterpret_cast<uint64_t*>(coeffs), (unsigned)src_domain.log2_size,
                                        (unsigned)target_domain.log2_size, num_roots_cut_out_of_vanishing_polynomial) != BBG_OK)
         fail("bbg_divide_by_pseudo_vanishing");
+}
+void transform_srs(g1::affine_element* monomials, g1::affine_element* lagrange_base_affine, const size_t degree)
+{
+    std::lock_guard<std::mutex> lk(state().mu);
+    if (degree < 2 || (degree & (degree - 1)) != 0) throw std::runtime_error("transform_srs: degree must be a power of two >= 2");
+    bbg_srs *mono = nullptr, *lagrange = nullptr;
+    if (bbg_srs_register(context(), reinterpret_cast<const uint64_t*>(monomials), degree, sizeof(g1::affine_element), &mono) != BBG_OK)
+        fail("bbg_srs_register");
+    int rc = bbg_srs_lagrange(context(), mono, (unsigned)__builtin_ctzll(degree), &lagrange);
+    bbg_srs_free(mono);
+    if (rc != BBG_OK) fail("bbg_srs_lagrange");
+    rc = bbg_srs_read(lagrange, 0, degree, reinterpret_cast<uint64_t*>(lagrange_base_affine));
+    bbg_srs_free(lagrange);
+    if (rc != BBG_OK) fail("bbg_srs_read");
 }
 } // namespace bbg_shim
