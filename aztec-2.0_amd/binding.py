@@ -61,6 +61,7 @@ def load_library():
         "bbg_srs_register_device": (cint, [vp, vp, sz, ctypes.POINTER(vp)]),
         "bbg_srs_synth_linear": (cint, [vp, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(vp)]),
         "bbg_srs_synth_hashed": (cint, [vp, ctypes.c_uint64, sz, ctypes.POINTER(vp)]),
+        "bbg_srs_synth_powers": (cint, [vp, vp, sz, ctypes.POINTER(vp)]),
         "bbg_srs_load_transcript": (cint, [vp, ctypes.c_char_p, sz, ctypes.POINTER(vp)]),
         "bbg_srs_register_transcript_buffer": (cint, [vp, vp, sz, ctypes.POINTER(vp)]),
         "bbg_srs_write_transcript": (cint, [vp, ctypes.c_char_p, sz, vp]),
@@ -82,6 +83,8 @@ def load_library():
         "bbg_g1_sum": (cint, [vp, vp, sz, vp]),
         "bbg_g1_sum_device": (cint, [vp, vp, sz, vp]),
         "bbg_g1_normalize": (cint, [vp, vp, sz, vp]),
+        "bbg_g1_fixed_base_mul": (cint, [vp, vp, vp, sz, vp]),
+        "bbg_g1_fixed_base_mul_device": (cint, [vp, vp, vp, sz, vp]),
         "bbg_ntt": (cint, [vp, vp, ctypes.c_uint, cint, sz, vp]),
         "bbg_coset_fft_extend": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp]),
         "bbg_quotient_widget_device": (cint, [vp, cint, vp, ctypes.c_uint, vp, vp, vp]),
@@ -157,6 +160,7 @@ EXPORTED_SYMBOLS = [
     "bbg_prover_round4", "bbg_prover_evaluate", "bbg_prover_linearise", "bbg_prover_round6", "bbg_prover_read_poly",
     "bbg_multi_create", "bbg_multi_destroy", "bbg_multi_count", "bbg_multi_ctx", "bbg_multi_sync", "bbg_multi_srs_register",
     "bbg_multi_srs_synth_hashed", "bbg_multi_srs_num_points", "bbg_multi_msm", "bbg_multi_ntt_device", "bbg_multi_ntt", "bbg_multi_set_option",
+    "bbg_g1_fixed_base_mul", "bbg_g1_fixed_base_mul_device", "bbg_srs_synth_powers",
 ]
 
 
@@ -265,6 +269,13 @@ class Bbg:
         self._ck(self.lib.bbg_srs_synth_hashed(self.ctx, seed, n, ctypes.byref(h)))
         return Srs(self, h)
 
+    def srs_synth_powers(self, x, n):
+        """The structured string P_i = [x^i] G, i < n, for a known x (Montgomery Fr limbs) (bbg_srs_synth_powers)."""
+        xx = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+        h = ctypes.c_void_p()
+        self._ck(self.lib.bbg_srs_synth_powers(self.ctx, xx.ctypes.data, n, ctypes.byref(h)))
+        return Srs(self, h)
+
     def srs_load_transcript(self, directory, num_points):
         h = ctypes.c_void_p()
         self._ck(self.lib.bbg_srs_load_transcript(self.ctx, str(directory).encode(), num_points, ctypes.byref(h)))
@@ -339,6 +350,20 @@ class Bbg:
         out = np.zeros((j.shape[0], 8), dtype=np.uint64)
         self._ck(self.lib.bbg_g1_normalize(self.ctx, j.ctypes.data, j.shape[0], out.ctypes.data))
         return out
+
+    def g1_fixed_base_mul(self, scalars, base=None):
+        """scalars[i] * base as (n, 8) canonical affine points; base = one affine point (8 limbs), None = the generator
+        (bbg_g1_fixed_base_mul)."""
+        sc = _u64(scalars, 4)
+        b = None if base is None else np.ascontiguousarray(base, dtype=np.uint64).reshape(8)
+        out = np.zeros((sc.shape[0], 8), dtype=np.uint64)
+        self._ck(self.lib.bbg_g1_fixed_base_mul(self.ctx, None if b is None else b.ctypes.data, sc.ctypes.data, sc.shape[0], out.ctypes.data))
+        return out
+
+    def g1_fixed_base_mul_device(self, d_scalars, n, d_out, base=None):
+        b = None if base is None else np.ascontiguousarray(base, dtype=np.uint64).reshape(8)
+        self._ck(self.lib.bbg_g1_fixed_base_mul_device(self.ctx, None if b is None else b.ctypes.data, ctypes.c_void_p(d_scalars), n,
+                                                       ctypes.c_void_p(d_out)))
 
     # ---- NTT
     def ntt(self, coeffs, op=FFT, generator_size=0, constant=None):

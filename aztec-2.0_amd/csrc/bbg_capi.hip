@@ -153,6 +153,7 @@ void bbg_destroy(bbg_ctx* ctx)
     if (ctx->msm.buf) (void)hipFree(ctx->msm.buf);
     if (ctx->msm_tiny.buf) (void)hipFree(ctx->msm_tiny.buf);
     if (ctx->poly_scratch) (void)hipFree(ctx->poly_scratch);
+    if (ctx->fb_table) (void)hipFree(ctx->fb_table);
     if (ctx->aux_stream) {
         for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
             (void)hipStreamDestroy(ctx->aux_streams[k]);
@@ -382,7 +383,7 @@ int bbg_memory_report(bbg_ctx* ctx, bbg_memory_info* out)
     for (const auto& kv : ctx->dpv_tables) out->ntt_tables += (size_t)32 << ((kv.first >> 8) & 0xff); // poly_dpv_table: one Fr per target-domain point
     out->msm_arena = ctx->msm.bytes + ctx->msm_tiny.bytes;
     out->scratch = ctx->ntt_scratch_bytes + ctx->staging_bytes + ctx->poly_scratch_bytes + ctx->gp_totals_bytes + ctx->quot_setup_bytes +
-                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES;
+                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES + ctx->fb_table_bytes;
     prover_report(ctx, &out->prover_keys, &out->live_provers);
     out->total = out->srs_points + out->srs_tables + out->ntt_tables + out->msm_arena + out->scratch + out->prover_keys;
     BBG_HIP(hipMemGetInfo(&out->device_free, &out->device_total));
@@ -414,6 +415,8 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released)
         drop(&ctx->poly_scratch, &ctx->poly_scratch_bytes);
         drop(&ctx->gp_totals, &ctx->gp_totals_bytes);
         drop(&ctx->quot_setup, &ctx->quot_setup_bytes);
+        drop(&ctx->fb_table, &ctx->fb_table_bytes); // the next fixed-base call rebuilds it
+        ctx->fb_table_valid = false;
         drop(&ctx->msm.buf, &ctx->msm.bytes);
         drop(&ctx->msm_tiny.buf, &ctx->msm_tiny.bytes);
         ctx->msm_tiny_layout = 0;
@@ -562,6 +565,35 @@ int bbg_srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, bbg_srs** out)
     if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, out);
     (void)hipFree(d_plain);
     return rc;
+}
+
+// Structured string P_i = [x^i] G: the powers x^i on the device (32 n bytes of working memory, freed before return), then the fixed-base
+// multiplication by the generator's table straight into the plain-point buffer (fixed_base.hip).
+int bbg_srs_synth_powers(bbg_ctx* ctx, const uint64_t x[4], size_t n, bbg_srs** out)
+{
+    CHECK_CTX(ctx);
+    if (!out || !x) { set_error("bbg_srs_synth_powers: null argument"); return BBG_E_INVALID; }
+    if (n == 0) { set_error("bbg_srs_synth_powers: n must be at least 1"); return BBG_E_INVALID; }
+    static const uint64_t R_MOD[4] = { 0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL };
+    if ((x[0] | x[1] | x[2] | x[3]) == 0 || memcmp(x, R_MOD, 32) == 0) { // the two representatives of 0 in [0, 2r)
+        set_error("bbg_srs_synth_powers: x = 0 (P_1 would be the point at infinity)");
+        return BBG_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    void *d_plain = nullptr, *d_pow = nullptr;
+    bbg_srs* res = nullptr;
+    int rc = BBG_OK;
+    hipError_t e = hipMalloc(&d_plain, n * 64);
+    if (e == hipSuccess) e = hipMalloc(&d_pow, n * 32);
+    if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_synth_powers: working set", __FILE__, __LINE__);
+    if (rc == BBG_OK) rc = fixed_base_powers(x, n, d_pow, ctx->stream);
+    if (rc == BBG_OK) rc = fixed_base_mul(ctx, nullptr, d_pow, n, d_plain, ctx->stream);
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
+    if (d_pow) (void)hipFree(d_pow);
+    if (d_plain) (void)hipFree(d_plain);
+    if (rc) return rc;
+    *out = res;
+    return BBG_OK;
 }
 
 // pts: num_points x 8 limbs in STANDARD (non-Montgomery) form, slot 0 free: sets monomials[0] = G = (1, 2), converts to Montgomery form
@@ -968,6 +1000,30 @@ int bbg_g1_normalize(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t
     rc = g1_normalize_device(st, n, st + n * 96, ctx->stream);
     if (rc) return rc;
     BBG_HIP(hipMemcpyAsync(out_affine, st + n * 96, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
+int bbg_g1_fixed_base_mul_device(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scalars, size_t n, void* d_out_affine)
+{
+    CHECK_CTX(ctx);
+    if ((!d_scalars || !d_out_affine) && n) { set_error("bbg_g1_fixed_base_mul_device: null argument"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return fixed_base_mul(ctx, base_affine, d_scalars, n, d_out_affine, ctx->stream);
+}
+
+int bbg_g1_fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine)
+{
+    CHECK_CTX(ctx);
+    if ((!scalars || !out_affine) && n) { set_error("bbg_g1_fixed_base_mul: null argument"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 96 + 64);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging; // scalars | results
+    if (n) BBG_HIP(hipMemcpyAsync(st, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = fixed_base_mul(ctx, base_affine, st, n, st + n * 32, ctx->stream); // validates the base for n = 0 as well
+    if (rc || n == 0) return rc;
+    BBG_HIP(hipMemcpyAsync(out_affine, st + n * 32, n * 64, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }

@@ -148,6 +148,11 @@ struct bbg_ctx {
     bool ntt_attr29_set = false;
     bool ntt_attr8s_set = false;
     bool ntt_attr8_set = false, ntt_attr_set = false; // dynamic-LDS attributes of the pass kernels set on this context's device
+    // fixed_base.hip: the table T[w][d-1] = d 2^(8w) B of the base point last used (one slot: another base rebuilds it in place)
+    void* fb_table = nullptr;
+    size_t fb_table_bytes = 0;
+    uint64_t fb_table_key[8] = {}; // the base's canonical bytes
+    bool fb_table_valid = false;
 };
 
 struct bbg_srs {
@@ -226,4 +231,10 @@ int g1_sum_device(bbg_ctx* ctx, const void* d_jacs, size_t n, void* d_out, hipSt
 // d_out: 2^log2n x 64 B canonical affine; *d_inf_flag (cleared by the caller on `stream`) is set when an output is the point at infinity.
 // Queues only, no host synchronisation.
 int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
+// fixed_base.hip: d_out[i] = d_scalars[i] * B (64 B canonical affine, aff_inf() for an infinite result) from the context's table of B's
+// multiples, which is built on first use and rebuilt for another base.  base_affine: HOST, NULL = the generator; BBG_E_INVALID when it is
+// not on the curve.  Queues only.
+int fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scalars, size_t n, void* d_out, hipStream_t stream);
+// d_out[i] = x^i, i < n (Montgomery Fr, coarse); x: host words.  Queues only.
+int fixed_base_powers(const uint64_t x[4], size_t n, void* d_out, hipStream_t stream);
 } // namespace bbg

@@ -74,6 +74,11 @@ int bbg_srs_synth_linear(bbg_ctx* ctx, uint64_t a, uint64_t s, size_t n, bbg_srs
 /* Synthetic SRS P_i = k_i*G, k_i = mix64(seed + i) | 1 (splitmix64 finaliser): no small linear relations between
  * the bases, which pippenger_unsafe requires of its inputs (scalar_multiplication.cpp:908-921). */
 int bbg_srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, bbg_srs** out);
+/* Structured SRS P_i = [x^i] G, i < n (P_0 = G): what a powers-of-tau ceremony outputs for a KNOWN x, i.e. a test / benchmark
+ * string.  x: Montgomery Fr on the host, [0, 2r).  x = 0 mod r -> BBG_E_INVALID (P_1 would be infinite), *out untouched.  n need not be
+ * a power of two.  The powers are made on the device and multiplied into G by bbg_g1_fixed_base_mul's kernels (32 n bytes of working
+ * memory beside the result, freed before return). */
+int bbg_srs_synth_powers(bbg_ctx* ctx, const uint64_t x[4], size_t n, bbg_srs** out);
 /* Reads an Ignition-format transcript file (manifest + big-endian points; srs/io.cpp:11-162): result is
  * monomials[0] = G followed by the file's points, num_points in total -- exactly read_transcript_g1. */
 int bbg_srs_load_transcript(bbg_ctx* ctx, const char* path, size_t num_points, bbg_srs** out);
@@ -133,6 +138,18 @@ int bbg_g1_sum(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t out_j
 int bbg_g1_sum_device(bbg_ctx* ctx, const void* d_jacobians, size_t n, void* d_out_jacobian);
 /* g1::affine_element(result) (element_impl.hpp:51-68) for n points; output canonical Montgomery affine (64 B each). */
 int bbg_g1_normalize(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t* out_affine);
+/* Fixed-base batch scalar multiplication (no counterpart in the reference, which loops over element::operator* on the host):
+ * out_affine[i] = scalars[i] * B for i < n.  base_affine: one 64-byte Montgomery affine point on the HOST (any
+ * representative in [0, 2p) per coordinate), NULL = the generator (1, 2).  scalars: Montgomery Fr, any representative in
+ * [0, 2r).  out: 64-byte canonical Montgomery affine points; a result that is the point at infinity (s = 0 mod r, or an
+ * infinite base) is written in the reference's affine encoding of infinity, exactly what aff_inf() in csrc/curve.hip.h
+ * writes (bit 63 of x.data[3] set, every other bit zero).  n = 0 is legal and does nothing.  A base that is not on the curve is
+ * BBG_E_INVALID.  A table of B's multiples d * 2^(8w) * B (510 KiB, counted under `scratch` in bbg_memory_report, released by
+ * bbg_memory_trim) is built on the first call and rebuilt when the base changes; each scalar then costs at most 32 mixed additions.
+ * Timed under "fixed_base_table" / "fixed_base_mul" (bbg_profile_get). */
+int bbg_g1_fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine);
+/* Device-resident: d_scalars and d_out_affine are device pointers, asynchronous on the context stream. */
+int bbg_g1_fixed_base_mul_device(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scalars, size_t n, void* d_out_affine);
 
 /* ---- NTT family: replaces polynomial_arithmetic::fft/ifft/coset_fft/coset_ifft/... on fr* coeffs
  *      (polynomials/polynomial_arithmetic.cpp:374-484) and the C bindings coset_fft_with_generator_shift / ifft
@@ -362,7 +379,7 @@ typedef struct bbg_memory_info {
     size_t srs_tables;     /* window tables of every live SRS of this context, all widths */
     size_t ntt_tables;     /* per-domain twiddle / coset tables (5 x 32n bytes per prepared size) */
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
-    size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants */
+    size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
@@ -405,7 +422,7 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
  * Every value of every option gives bit-identical results; they exist for A/B measurements. */
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
- * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize".  enable(…, 1) clears previous samples. */
+ * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
