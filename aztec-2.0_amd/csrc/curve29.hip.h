@@ -3,7 +3,7 @@
 //
 // All four coordinates live in R'-form (x * 2^261 mod p) as lazily reduced 9 x 29-bit values:
 //   at entry   X, Y < 32p, ZZ, ZZZ < 1.4p, limbs < 2^29 + 8    (a run starts from a table point: canonical, shifted by 5 bits)
-//   at exit    X < 20.4p, Y < 7.7p, ZZ, ZZZ < 1.1p, same limb bound
+//   at exit    X < 20.4p, Y < 7.7p, ZZ, ZZZ < 1.1p, exact limbs (< 2^29 below the top: every coordinate leaves a product's output masks)
 // (bounds: a product is < a * b / 2^261 + p and p / 2^261 = 2^-7.4; the inline comments carry them through).
 // The special cases of a complete addition (P = +-acc) are NOT tested per addition: both make PP = (U2 - X1)^2 a multiple of p, so
 // ZZ becomes a multiple of p and stays one under every later addition -- the caller tests ZZ once at the end of a run
@@ -60,24 +60,26 @@ __device__ __forceinline__ Xyzz29 xyzz29_from_affine(const Aff29& p)
 
 __device__ __forceinline__ Xyzz29 xyzz29_madd(const Xyzz29& a, const Aff29& p)
 {
-    // products in independent pairs (f29_mul2 ...: columns interleaved, see field29.hip.h)
-    Fq29 U2, S2, PP, RR, PPP, Q;
-    f29_mul2(p.x, a.zz, p.y, a.zzz, U2, S2);             // < 32 * 1.4 p * 2^-7.4 + p = 1.3p
-    const Fq29 P = f29_carry(f29_sub<34>(U2, a.x));      // U2 - X1 + 34p < 35.3p
-    const Fq29 R = f29_carry(f29_sub<34>(S2, a.y));      // < 35.3p
-    f29_sqr2(P, R, PP, RR);                              // < 35.3^2 * 2^-7.4 p + p = 8.4p
-    f29_mul2(P, PP, a.x, PP, PPP, Q);                    // PPP < 2.8p; Q < 32 * 8.4 * 2^-7.4 p + p = 2.6p
+    // Products in independent pairs (columns interleaved, see field29.hip.h).  The three sums whose operands exist before the product they follow
+    // starts -- P, R and X3 -- ride in that product's high columns (F29Job ADD): no f29_sub, no f29_carry, exact limbs.  T = Q - X3 cannot (Q and
+    // RR both precede X3, and T is an OPERAND of the product after it); its carry pass stays, because uncarried limbs < 2^31 against R would put
+    // column 8 of Y3 at 9 * 2^60 + 27 * 2^58 + 9 * 2^58 > 2^63.  Column sums: tests/test_acc29_bounds_cpu.py (every product below 2^63).
+    Fq29 P, R, PPP, Q;
+    const Fq29 nx = f29_neg<34>(a.x), ny = f29_neg<34>(a.y); // 34p - X1, 34p - Y1: limbs < 2^31
+    f29_mul2_add(p.x, a.zz, nx, p.y, a.zzz, ny, P, R);       // U2, S2 < 32 * 1.4 p * 2^-7.4 + p = 1.3p; P = U2 - X1 + 34p, R = S2 - Y1 + 34p < 35.3p
+    const Fq29 PP = f29_sqr_z(P);                            // < 35.3^2 * 2^-7.4 p + p = 8.4p
+    f29_mul2_z(P, PP, a.x, PP, PPP, Q);                      // PPP < 2.8p; Q < 32 * 8.4 * 2^-7.4 p + p = 2.6p
     Xyzz29 r;
     // X3 = R^2 - PPP - 2Q + 12p: the subtrahend (< 8p) has limbs < 3 * 2^29, so this spread constant raises every limb by 2^31
     {
         Fq29 s;
 #pragma unroll
         for (int i = 0; i < 9; i++) s.v[i] = PPP.v[i] + 2 * Q.v[i];
-        r.x = f29_carry(f29_sub<12, 31>(RR, s));         // < 20.4p
+        const Fq29 ns = f29_neg<12, 31>(s);                  // limbs < 2^31 + 2^29
+        f29_sqr_add_mul(R, ns, a.zz, PP, r.x, r.zz);         // X3 = RR + 12p - s < 8.4p + 12p = 20.4p; ZZ3 < 1.4 * 8.4 * 2^-7.4 p + p = 1.1p
     }
-    const Fq29 T = f29_carry(f29_sub<24>(Q, r.x));       // Q - X3 + 24p < 26.6p
-    f29_mul_sub2_mul(R, T, a.y, PPP, a.zzz, PPP, r.y, r.zzz); // Y3 < (35.3 * 26.6 + 64 * 2.8) * 2^-7.4 p + p < 7.7p; ZZZ3 = ZZZ1 PPP
-    r.zz = f29_mul(a.zz, PP);                            // < 1.4 * 8.4 * 2^-7.4 p + p = 1.1p
+    const Fq29 T = f29_carry(f29_sub<24>(Q, r.x));           // Q - X3 + 24p < 26.6p
+    f29_mul_sub2_mul_z(R, T, a.y, PPP, a.zzz, PPP, r.y, r.zzz); // Y3 < (35.3 * 26.6 + 64 * 2.8) * 2^-7.4 p + p < 7.7p; ZZZ3 = ZZZ1 PPP
     return r;
 }
 

@@ -389,24 +389,43 @@ template <class P> __device__ __forceinline__ Fe<P> fe_mul29_ilp(const Fe<P>& a,
 // waves per SIMD (bench_micro/issue_rates.hip) -- 5 % of the bucket accumulation.  With two products in flight every statement is followed by
 // the other product's, and the independent chains also hide each other's latency.
 enum F29Shape { F29_MUL, F29_SQR, F29_MULSUB2 };
-template <class P, int SHAPE> struct F29Job {
+// ADD: the job also adds the 9 limbs at `add` (each < 2^32) to the RESULT, limb i into column 9 + i before that column closes, the top one into the
+// top limb: r = product + add with exact limbs (< 2^29 below the top) -- the output masks and column shifts the product pays anyway do the carry
+// pass an `f29_carry(f29_sub(product, b))` would run afterwards (8 mads with the constant 1 and one addition instead of 9 + 27 instructions).
+template <class P, int SHAPE, bool ADD = false> struct F29Job {
     const uint32_t *a, *b, *c, *d; // MUL: a * b; SQR: a * a (b = doubled a); MULSUB2: a * b + c * d (c already negated)
+    const uint32_t* add;
     uint64_t acc;
     uint32_t m[9];
     uint32_t* r;
 };
-template <class P, int SHAPE, int K> __device__ __forceinline__ void f29_job_terms(F29Job<P, SHAPE>& j)
+// acc = x * y: a run's first product without a zeroed accumulator in front of it (Z0 runs)
+__device__ __forceinline__ void mad1_zero(uint64_t& acc, uint32_t x, uint32_t y)
 {
-    if constexpr (SHAPE == F29_SQR) f29_sq_terms<K>(j.acc, j.a, j.b);
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=&v"(acc) : "v"(x), "v"(y) : "vcc");
+}
+// acc += x
+__device__ __forceinline__ void mad1_one(uint64_t& acc, uint32_t x)
+{
+    asm("v_mad_u64_u32 %0, vcc, %1, 1, %0" : "+v"(acc) : "v"(x) : "vcc");
+}
+template <class P, int SHAPE, bool ADD, int K, bool Z0> __device__ __forceinline__ void f29_job_terms(F29Job<P, SHAPE, ADD>& j)
+{
+    if constexpr (Z0 && K == 0) {
+        mad1_zero(j.acc, j.a[0], SHAPE == F29_SQR ? j.a[0] : j.b[0]);
+        if constexpr (SHAPE == F29_MULSUB2) mad1_v(j.acc, j.c[0], j.d[0]);
+    } else if constexpr (SHAPE == F29_SQR) f29_sq_terms<K>(j.acc, j.a, j.b);
     else {
         f29_ab_terms<K>(j.acc, j.a, j.b);
         if constexpr (SHAPE == F29_MULSUB2) f29_ab_terms<K>(j.acc, j.c, j.d);
     }
+    if constexpr (ADD && K >= 9) mad1_one(j.acc, j.add[K - 9]);
 }
-template <class P, int S1, int S2, int K> __device__ __forceinline__ void f29_pair_column(F29Job<P, S1>& x, F29Job<P, S2>& y)
+template <class P, int S1, bool A1, int S2, bool A2, int K, bool Z0>
+__device__ __forceinline__ void f29_pair_column(F29Job<P, S1, A1>& x, F29Job<P, S2, A2>& y)
 {
-    f29_job_terms<P, S1, K>(x);
-    f29_job_terms<P, S2, K>(y);
+    f29_job_terms<P, S1, A1, K, Z0>(x);
+    f29_job_terms<P, S2, A2, K, Z0>(y);
     f29_mp_terms<P, K>(x.acc, x.m);
     f29_mp_terms<P, K>(y.acc, y.m);
     if constexpr (K <= 8) {
@@ -418,18 +437,31 @@ template <class P, int S1, int S2, int K> __device__ __forceinline__ void f29_pa
         x.r[K - 9] = (uint32_t)x.acc & M29;
         y.r[K - 9] = (uint32_t)y.acc & M29;
     }
-    asm("v_lshrrev_b64 %0, 29, %0" : "+v"(x.acc));
-    asm("v_lshrrev_b64 %0, 29, %0" : "+v"(y.acc));
+    if constexpr (Z0 && K > 8) {
+        // the limb as an input the statement does not use: the mask is taken BEFORE the shift (scheduled after it, it keeps the unshifted sum alive
+        // in a copy: a v_mov_b64 per column in some runs)
+        asm("v_lshrrev_b64 %0, 29, %0" : "+v"(x.acc) : "v"(x.r[K - 9]));
+        asm("v_lshrrev_b64 %0, 29, %0" : "+v"(y.acc) : "v"(y.r[K - 9]));
+    } else {
+        asm("v_lshrrev_b64 %0, 29, %0" : "+v"(x.acc));
+        asm("v_lshrrev_b64 %0, 29, %0" : "+v"(y.acc));
+    }
 }
-template <class P, int S1, int S2> __device__ __forceinline__ void f29_pair_run(F29Job<P, S1>& x, F29Job<P, S2>& y)
+// Z0: column 0 starts its accumulators with mad1_zero (the bucket accumulation's runs; the NTT and the widgets keep the zeroed accumulators)
+template <bool Z0 = false, class P, int S1, bool A1, int S2, bool A2>
+__device__ __forceinline__ void f29_pair_run(F29Job<P, S1, A1>& x, F29Job<P, S2, A2>& y)
 {
-    x.acc = 0;
-    y.acc = 0;
-#define BBG_X(K) f29_pair_column<P, S1, S2, K>(x, y);
+    if constexpr (!Z0) {
+        x.acc = 0;
+        y.acc = 0;
+    }
+#define BBG_X(K) f29_pair_column<P, S1, A1, S2, A2, K, Z0>(x, y);
     BBG_F29_COLUMNS(BBG_X)
 #undef BBG_X
     x.r[8] = (uint32_t)x.acc;
     y.r[8] = (uint32_t)y.acc;
+    if constexpr (A1) x.r[8] += x.add[8];
+    if constexpr (A2) y.r[8] += y.add[8];
 }
 // r1 = a1 * b1, r2 = a2 * b2
 template <class P> __device__ __forceinline__ void f29_mul2(const F29<P>& a1, const F29<P>& b1, const F29<P>& a2, const F29<P>& b2, F29<P>& r1, F29<P>& r2)
@@ -468,5 +500,75 @@ __device__ __forceinline__ void f29_mul_sub2_mul(const F29<P>& a, const F29<P>& 
     y.a = e.v, y.b = f.v, y.r = r2.v;
     f29_pair_run(x, y);
 }
+
+// ---- the products of the bucket accumulation's mixed addition (curve29.hip.h): Z0 runs, sums folded into the product that precedes them.
+// M p - b limbwise (f29_sub from zero): the addend of a folded a - b + M p
+template <int K, int E = 30, class P> __device__ __forceinline__ F29<P> f29_neg(const F29<P>& b)
+{
+    F29<P> z;
+#pragma unroll
+    for (int i = 0; i < 9; i++) z.v[i] = 0;
+    return f29_sub<K, E>(z, b);
+}
+// r1 = a1 * b1, r2 = a2 * b2
+template <class P> __device__ __forceinline__ void f29_mul2_z(const F29<P>& a1, const F29<P>& b1, const F29<P>& a2, const F29<P>& b2, F29<P>& r1, F29<P>& r2)
+{
+    F29Job<P, F29_MUL> x, y;
+    x.a = a1.v, x.b = b1.v, x.r = r1.v;
+    y.a = a2.v, y.b = b2.v, y.r = r2.v;
+    f29_pair_run<true>(x, y);
+}
+// r1 = a1 * b1 + d1, r2 = a2 * b2 + d2, exact limbs
+template <class P>
+__device__ __forceinline__ void f29_mul2_add(const F29<P>& a1, const F29<P>& b1, const F29<P>& d1, const F29<P>& a2, const F29<P>& b2, const F29<P>& d2,
+                                             F29<P>& r1, F29<P>& r2)
+{
+    F29Job<P, F29_MUL, true> x, y;
+    x.a = a1.v, x.b = b1.v, x.add = d1.v, x.r = r1.v;
+    y.a = a2.v, y.b = b2.v, y.add = d2.v, y.r = r2.v;
+    f29_pair_run<true>(x, y);
+}
+// r1 = a^2 + d (exact limbs), r2 = e * f
+template <class P>
+__device__ __forceinline__ void f29_sqr_add_mul(const F29<P>& a, const F29<P>& d, const F29<P>& e, const F29<P>& f, F29<P>& r1, F29<P>& r2)
+{
+    uint32_t a2[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) a2[i] = a.v[i] << 1;
+    F29Job<P, F29_SQR, true> x;
+    F29Job<P, F29_MUL> y;
+    x.a = a.v, x.b = a2, x.add = d.v, x.r = r1.v;
+    y.a = e.v, y.b = f.v, y.r = r2.v;
+    f29_pair_run<true>(x, y);
+}
+// r1 = a * b - c * d (as f29_mul_sub2), r2 = e * f
+template <class P>
+__device__ __forceinline__ void f29_mul_sub2_mul_z(const F29<P>& a, const F29<P>& b, const F29<P>& c, const F29<P>& d, const F29<P>& e, const F29<P>& f,
+                                                   F29<P>& r1, F29<P>& r2)
+{
+    const F29<P> nc = f29_neg<64, 30>(c);
+    F29Job<P, F29_MULSUB2> x;
+    F29Job<P, F29_MUL> y;
+    x.a = a.v, x.b = b.v, x.c = nc.v, x.d = d.v, x.r = r1.v;
+    y.a = e.v, y.b = f.v, y.r = r2.v;
+    f29_pair_run<true>(x, y);
+}
+// a^2, the one product of the mixed addition that runs alone
+template <class P> __device__ __forceinline__ F29<P> f29_sqr_z(const F29<P>& a)
+{
+    uint64_t acc;
+    uint32_t m[9], d[9];
+    F29<P> r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) d[i] = a.v[i] << 1;
+    mad1_zero(acc, a.v[0], a.v[0]);
+    f29_close_column<P, 0>(acc, m, r.v);
+#define BBG_X(K) f29_sq_terms<K>(acc, a.v, d); f29_close_column<P, K>(acc, m, r.v);
+    BBG_X(1) BBG_X(2) BBG_X(3) BBG_X(4) BBG_X(5) BBG_X(6) BBG_X(7) BBG_X(8) BBG_X(9) BBG_X(10) BBG_X(11) BBG_X(12) BBG_X(13) BBG_X(14) BBG_X(15) BBG_X(16)
+#undef BBG_X
+    r.v[8] = (uint32_t)acc;
+    return r;
+}
+
 
 } // namespace bbg
