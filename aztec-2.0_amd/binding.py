@@ -85,6 +85,9 @@ def load_library():
         "bbg_g1_normalize": (cint, [vp, vp, sz, vp]),
         "bbg_g1_fixed_base_mul": (cint, [vp, vp, vp, sz, vp]),
         "bbg_g1_fixed_base_mul_device": (cint, [vp, vp, vp, sz, vp]),
+        "bbg_g1_batch_mul": (cint, [vp, vp, vp, sz, cint, vp]),
+        "bbg_g1_batch_mul_device": (cint, [vp, vp, vp, sz, cint, vp]),
+        "bbg_srs_scale_powers": (cint, [vp, vp, vp, ctypes.POINTER(vp)]),
         "bbg_ntt": (cint, [vp, vp, ctypes.c_uint, cint, sz, vp]),
         "bbg_coset_fft_extend": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp]),
         "bbg_quotient_widget_device": (cint, [vp, cint, vp, ctypes.c_uint, vp, vp, vp]),
@@ -161,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "bbg_multi_create", "bbg_multi_destroy", "bbg_multi_count", "bbg_multi_ctx", "bbg_multi_sync", "bbg_multi_srs_register",
     "bbg_multi_srs_synth_hashed", "bbg_multi_srs_num_points", "bbg_multi_msm", "bbg_multi_ntt_device", "bbg_multi_ntt", "bbg_multi_set_option",
     "bbg_g1_fixed_base_mul", "bbg_g1_fixed_base_mul_device", "bbg_srs_synth_powers",
+    "bbg_g1_batch_mul", "bbg_g1_batch_mul_device", "bbg_srs_scale_powers",
 ]
 
 
@@ -203,6 +207,13 @@ class Srs:
         """The Lagrange-base form of the first 2^log2n points, LB[k] = n^-1 sum_j w_n^(-jk) M_j, as an Srs of its own (bbg_srs_lagrange)."""
         h = ctypes.c_void_p()
         self._owner._ck(self._owner.lib.bbg_srs_lagrange(self._owner.ctx, self.handle, log2n, ctypes.byref(h)))
+        return Srs(self._owner, h)
+
+    def scale_powers(self, y):
+        """The string with P_i' = [y^i] P_i as an Srs of its own; y: Montgomery Fr limbs (bbg_srs_scale_powers)."""
+        yy = np.ascontiguousarray(y, dtype=np.uint64).reshape(4)
+        h = ctypes.c_void_p()
+        self._owner._ck(self._owner.lib.bbg_srs_scale_powers(self._owner.ctx, self.handle, yy.ctypes.data, ctypes.byref(h)))
         return Srs(self._owner, h)
 
     def free(self):
@@ -364,6 +375,19 @@ class Bbg:
         b = None if base is None else np.ascontiguousarray(base, dtype=np.uint64).reshape(8)
         self._ck(self.lib.bbg_g1_fixed_base_mul_device(self.ctx, None if b is None else b.ctypes.data, ctypes.c_void_p(d_scalars), n,
                                                        ctypes.c_void_p(d_out)))
+
+    def g1_batch_mul(self, points, scalars, one_scalar=False):
+        """scalars[i] * points[i] (one_scalar: scalars[0] * points[i]) as (n, 8) canonical affine points (bbg_g1_batch_mul)."""
+        pt, sc = _u64(points, 8), _u64(scalars, 4)
+        if sc.shape[0] != (1 if one_scalar else pt.shape[0]):
+            raise ValueError("one scalar per point, or exactly one with one_scalar")
+        out = np.zeros((pt.shape[0], 8), dtype=np.uint64)
+        self._ck(self.lib.bbg_g1_batch_mul(self.ctx, pt.ctypes.data, sc.ctypes.data, pt.shape[0], int(bool(one_scalar)), out.ctypes.data))
+        return out
+
+    def g1_batch_mul_device(self, d_points, d_scalars, n, d_out, one_scalar=False):
+        self._ck(self.lib.bbg_g1_batch_mul_device(self.ctx, ctypes.c_void_p(d_points), ctypes.c_void_p(d_scalars), n, int(bool(one_scalar)),
+                                                  ctypes.c_void_p(d_out)))
 
     # ---- NTT
     def ntt(self, coeffs, op=FFT, generator_size=0, constant=None):

@@ -154,6 +154,7 @@ void bbg_destroy(bbg_ctx* ctx)
     if (ctx->msm_tiny.buf) (void)hipFree(ctx->msm_tiny.buf);
     if (ctx->poly_scratch) (void)hipFree(ctx->poly_scratch);
     if (ctx->fb_table) (void)hipFree(ctx->fb_table);
+    if (ctx->vb_tables) (void)hipFree(ctx->vb_tables);
     if (ctx->aux_stream) {
         for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
             (void)hipStreamDestroy(ctx->aux_streams[k]);
@@ -238,6 +239,21 @@ int bbg_set_option(bbg_ctx* ctx, const char* key, long value)
     if (!strcmp(key, "msm_upload_pieces")) { // bbg_msm: pieces the host scalars travel in (1 = one copy in front of the MSM)
         if (value < 1 || value > bbg_ctx::UPLOAD_PIECES) { set_error("bbg_set_option: msm_upload_pieces must be 1..4"); return BBG_E_INVALID; }
         ctx->msm_upload_pieces = (int)value;
+        return BBG_OK;
+    }
+    if (!strcmp(key, "batch_mul_glv")) { // bbg_g1_batch_mul: 1 = windowed GLV, 0 = bit-serial double-and-add (A/B)
+        if (value != 0 && value != 1) { set_error("batch_mul_glv: 0 or 1"); return BBG_E_INVALID; }
+        ctx->batch_mul_glv = (int)value;
+        return BBG_OK;
+    }
+    if (!strcmp(key, "ecntt_mul")) { // bbg_srs_lagrange: 1 = the stages multiply with the windowed GLV form, 0 = bit-serial (A/B)
+        if (value != 0 && value != 1) { set_error("ecntt_mul: 0 or 1"); return BBG_E_INVALID; }
+        ctx->ecntt_mul = (int)value;
+        return BBG_OK;
+    }
+    if (!strcmp(key, "batch_mul_lanes")) { // lanes of the variable-base kernels = 1 KiB tables held; a launch-time choice
+        if (value < 64 || value > (1L << 20) || value % 64) { set_error("batch_mul_lanes: a multiple of 64 in 64 .. 2^20"); return BBG_E_INVALID; }
+        ctx->batch_mul_lanes = value;
         return BBG_OK;
     }
     if (!strcmp(key, "msm_reduce_quad")) {
@@ -383,7 +399,7 @@ int bbg_memory_report(bbg_ctx* ctx, bbg_memory_info* out)
     for (const auto& kv : ctx->dpv_tables) out->ntt_tables += (size_t)32 << ((kv.first >> 8) & 0xff); // poly_dpv_table: one Fr per target-domain point
     out->msm_arena = ctx->msm.bytes + ctx->msm_tiny.bytes;
     out->scratch = ctx->ntt_scratch_bytes + ctx->staging_bytes + ctx->poly_scratch_bytes + ctx->gp_totals_bytes + ctx->quot_setup_bytes +
-                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES + ctx->fb_table_bytes;
+                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES + ctx->fb_table_bytes + ctx->vb_tables_bytes;
     prover_report(ctx, &out->prover_keys, &out->live_provers);
     out->total = out->srs_points + out->srs_tables + out->ntt_tables + out->msm_arena + out->scratch + out->prover_keys;
     BBG_HIP(hipMemGetInfo(&out->device_free, &out->device_total));
@@ -417,6 +433,7 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released)
         drop(&ctx->quot_setup, &ctx->quot_setup_bytes);
         drop(&ctx->fb_table, &ctx->fb_table_bytes); // the next fixed-base call rebuilds it
         ctx->fb_table_valid = false;
+        drop(&ctx->vb_tables, &ctx->vb_tables_bytes);
         drop(&ctx->msm.buf, &ctx->msm.bytes);
         drop(&ctx->msm_tiny.buf, &ctx->msm_tiny.bytes);
         ctx->msm_tiny_layout = 0;
@@ -588,6 +605,38 @@ int bbg_srs_synth_powers(bbg_ctx* ctx, const uint64_t x[4], size_t n, bbg_srs** 
     if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_synth_powers: working set", __FILE__, __LINE__);
     if (rc == BBG_OK) rc = fixed_base_powers(x, n, d_pow, ctx->stream);
     if (rc == BBG_OK) rc = fixed_base_mul(ctx, nullptr, d_pow, n, d_plain, ctx->stream);
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
+    if (d_pow) (void)hipFree(d_pow);
+    if (d_plain) (void)hipFree(d_plain);
+    if (rc) return rc;
+    *out = res;
+    return BBG_OK;
+}
+
+// The update step of a powers-of-x string, P_i' = [y^i] P_i: the powers y^i on the device (k_fb_powers), the variable-base batch
+// multiplication (var_base.hip) from the SRS's plain points into a fresh buffer, then the registration.  32 n bytes of working memory
+// beside the result and the lanes' tables.
+int bbg_srs_scale_powers(bbg_ctx* ctx, bbg_srs* srs, const uint64_t y[4], bbg_srs** out)
+{
+    CHECK_CTX(ctx);
+    if (!srs || !y || !out) { set_error("bbg_srs_scale_powers: null argument"); return BBG_E_INVALID; }
+    if (srs->s.device != ctx->device) { set_error("bbg_srs_scale_powers: the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    static const uint64_t R_MOD[4] = { 0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL };
+    if ((y[0] | y[1] | y[2] | y[3]) == 0 || memcmp(y, R_MOD, 32) == 0) { // the two representatives of 0 in [0, 2r)
+        set_error("bbg_srs_scale_powers: y = 0 (P_1 would become the point at infinity)");
+        return BBG_E_INVALID;
+    }
+    const size_t n = srs->s.n;
+    if (n == 0) { set_error("bbg_srs_scale_powers: the SRS is empty"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    void *d_plain = nullptr, *d_pow = nullptr;
+    bbg_srs* res = nullptr;
+    int rc = BBG_OK;
+    hipError_t e = hipMalloc(&d_plain, n * 64);
+    if (e == hipSuccess) e = hipMalloc(&d_pow, n * 32);
+    if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_scale_powers: working set", __FILE__, __LINE__);
+    if (rc == BBG_OK) rc = fixed_base_powers(y, n, d_pow, ctx->stream);
+    if (rc == BBG_OK) rc = var_base_mul(ctx, srs->s.points, d_pow, n, 0, d_plain, ctx->stream);
     if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
     if (d_pow) (void)hipFree(d_pow);
     if (d_plain) (void)hipFree(d_plain);
@@ -1024,6 +1073,33 @@ int bbg_g1_fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint6
     rc = fixed_base_mul(ctx, base_affine, st, n, st + n * 32, ctx->stream); // validates the base for n = 0 as well
     if (rc || n == 0) return rc;
     BBG_HIP(hipMemcpyAsync(out_affine, st + n * 32, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
+int bbg_g1_batch_mul_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int one_scalar, void* d_out_affine)
+{
+    CHECK_CTX(ctx);
+    if ((!d_points_affine || !d_scalars || !d_out_affine) && n) { set_error("bbg_g1_batch_mul_device: null argument"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return var_base_mul(ctx, d_points_affine, d_scalars, n, one_scalar, d_out_affine, ctx->stream);
+}
+
+int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t* scalars, size_t n, int one_scalar, uint64_t* out_affine)
+{
+    CHECK_CTX(ctx);
+    if ((!points_affine || !scalars || !out_affine) && n) { set_error("bbg_g1_batch_mul: null argument"); return BBG_E_INVALID; }
+    if (n == 0) return BBG_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t ns = one_scalar ? 1 : n;
+    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 64 + ns * 32);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging; // points (multiplied in place) | scalars
+    BBG_HIP(hipMemcpyAsync(st, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(st + n * 64, scalars, ns * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = var_base_mul(ctx, st, st + n * 64, n, one_scalar, st, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out_affine, st, n * 64, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }

@@ -153,6 +153,13 @@ struct bbg_ctx {
     size_t fb_table_bytes = 0;
     uint64_t fb_table_key[8] = {}; // the base's canonical bytes
     bool fb_table_valid = false;
+    // var_base.hip: the lanes' tables of odd multiples (1 KiB per lane) of the windowed GLV multiplication, shared by bbg_g1_batch_mul and
+    // the Lagrange transform's stages under "ecntt_mul" = 1
+    void* vb_tables = nullptr;
+    size_t vb_tables_bytes = 0;
+    int batch_mul_glv = 1;           // option "batch_mul_glv": 1 = windowed GLV (xyzz_mul_glv), 0 = the bit-serial double-and-add (xyzz_mul_fr), A/B
+    long batch_mul_lanes = 1L << 17; // option "batch_mul_lanes": lanes of the variable-base kernels = tables held (a multiple of 64; 2^17 = two waves per SIMD)
+    int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
 };
 
 struct bbg_srs {
@@ -237,4 +244,10 @@ int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, voi
 int fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scalars, size_t n, void* d_out, hipStream_t stream);
 // d_out[i] = x^i, i < n (Montgomery Fr, coarse); x: host words.  Queues only.
 int fixed_base_powers(const uint64_t x[4], size_t n, void* d_out, hipStream_t stream);
+// var_base.hip: d_out[i] = d_scalars[one_scalar ? 0 : i] * d_points[i] (64 B Montgomery affine in, canonical out, aff_inf() for an
+// infinite result).  d_out may be d_points; any other overlap, and any overlap of d_out with the scalars, is BBG_E_INVALID.  Queues only.
+int var_base_mul(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size_t n, int one_scalar, void* d_out, hipStream_t stream);
+// the lanes (a multiple of 64, at most "batch_mul_lanes") a variable-base kernel with `work` items runs on, and their tables in the
+// context's buffer (1 KiB per lane, grown on demand)
+int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables);
 } // namespace bbg

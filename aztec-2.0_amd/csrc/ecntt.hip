@@ -17,40 +17,19 @@
 //                      integer by a left-to-right double-and-add on the complete XYZZ formulas of curve.hip.h.  Butterflies whose
 //                      twiddle is 1 skip the multiplication (all of stage 0).  The LAST stage carries n^-1: its twiddles are n^-1 w
 //                      and its A operands are multiplied by n^-1 (n/2 extra scalar multiplications, 1 / log2 n of the work, and no
-//                      pass of its own);
+//                      pass of its own).  By default (option "ecntt_mul" = 1) the stages run on the windowed GLV multiplication of
+//                      var_base.hip.h instead (k_ecntt_stage_glv: 2.2x at 2^20, profiles/var_base.txt); 0 = this kernel, A/B;
 //   * k_ecntt_normalize  batched conversion to canonical affine, one inversion per NORM_CH points; a point at infinity among the
 //                      outputs raises a flag (an SRS handle never holds one) and the call fails.
 // All group-law cases (equal / opposite operands, infinities inside the transform) are handled by xyzz_add / xyzz_dbl.
 #include "bbg_internal.h"
 #include "curve.hip.h"
 #include "ntt_consts.hip.h"
+#include "var_base.hip.h" // xyzz_mul_fr, xyzz_mul_glv, xyzz_neg
 
 namespace bbg {
 
 static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
-
-__device__ __forceinline__ Xyzz xyzz_neg(const Xyzz& p)
-{
-    Xyzz r = p;
-    r.y = fe_neg(p.y);
-    return r;
-}
-
-// k * P for a plain (non-Montgomery) canonical k < r < 2^254: left-to-right double-and-add.  The scalar is shifted left one bit per
-// step so that the bit under test is always bit 255: no runtime-indexed limb, and the loop body exists once.
-__device__ __forceinline__ Xyzz xyzz_mul_fr(const Xyzz& p, Fr k)
-{
-    Xyzz acc = xyzz_inf();
-    for (int i = 0; i < 256; i++) {
-        const bool bit = (k.v[7] >> 31) != 0;
-#pragma unroll
-        for (int l = 7; l > 0; l--) k.v[l] = (k.v[l] << 1) | (k.v[l - 1] >> 31);
-        k.v[0] <<= 1;
-        acc = xyzz_dbl(acc); // returns at once while acc is still infinity
-        if (bit) acc = xyzz_add(acc, p);
-    }
-    return acc;
-}
 
 __device__ __forceinline__ size_t bit_reverse(size_t i, unsigned bits)
 {
@@ -89,6 +68,33 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restr
     if (last) a = xyzz_mul_fr(a, fe_reduce_once(fe_from_mont(dc->n_inv)));
     xyzz_store(work + i, xyzz_add(a, b));
     xyzz_store(work + i + m, xyzz_add(a, xyzz_neg(b)));
+}
+
+// The same stage on the windowed GLV multiplication of var_base.hip.h (option "ecntt_mul" = 1, the default): a fixed number of lanes, each with its
+// 1 KiB table of odd multiples in `tables`, lane t taking the butterflies t, t + lanes, ..  Bit-identical to k_ecntt_stage after the
+// normalisation (the same group elements in another XYZZ representation).
+__global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last,
+                                                                       Xyzz* __restrict__ tables)
+{
+    const size_t lanes = (size_t)gridDim.x * blockDim.x;
+    const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Xyzz* table = tables + (size_t)blockIdx.x * 64 * GLV_TABLE; // the wave's 64 tables (blocks of one wave): wave-uniform
+    const size_t m = (size_t)1 << s;
+#pragma unroll 1
+    for (size_t t = lane; t < ((size_t)1 << (log2n - 1)); t += lanes) {
+        const size_t j = t & (m - 1);
+        const size_t i = ((t >> s) << (s + 1)) + j;
+        Xyzz b = xyzz_load(work + i + m);
+        if (last || j != 0) {
+            Fr w = pow_from_table(dc->pow2_root_inv, (uint64_t)j << (log2n - 1 - s)); // w_2m^-j = w_n^(-j n / 2m)
+            if (last) w = fe_mul(w, dc->n_inv);
+            b = xyzz_mul_glv(b, fe_reduce_once(fe_from_mont(w)), table);
+        }
+        Xyzz a = xyzz_load(work + i);
+        if (last) a = xyzz_mul_glv(a, fe_reduce_once(fe_from_mont(dc->n_inv)), table);
+        xyzz_store(work + i, xyzz_add(a, b));
+        xyzz_store(work + i + m, xyzz_add(a, xyzz_neg(b)));
+    }
 }
 
 // XYZZ -> canonical affine, NORM_CH consecutive points per thread behind one inversion (as k_srs_synth does).  A point at infinity is
@@ -142,12 +148,23 @@ int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, voi
     int rc = ntt_domain_consts(ctx, log2n, &consts); // root_inv^(2^b) and n^-1 of the scalar NTT's domain
     if (rc) return rc;
     const size_t n = (size_t)1 << log2n;
+    size_t lanes = 0;
+    void* tables = nullptr;
+    if (ctx->ecntt_mul) { // the lanes' tables of odd multiples (var_base.hip)
+        rc = var_base_tables(ctx, n / 2, &lanes, &tables);
+        if (rc) return rc;
+    }
     {
         ProfScope ps(ctx, "ecntt_stages", st);
         hipLaunchKernelGGL(k_ecntt_load, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Affine*)d_src, (Xyzz*)d_work, log2n);
-        for (unsigned s = 0; s < log2n; s++)
-            hipLaunchKernelGGL(k_ecntt_stage, dim3(grid_for(n / 2, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s,
-                               s + 1 == log2n ? 1 : 0);
+        for (unsigned s = 0; s < log2n; s++) {
+            const int last = s + 1 == log2n ? 1 : 0;
+            if (ctx->ecntt_mul)
+                hipLaunchKernelGGL(k_ecntt_stage_glv, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last,
+                                   (Xyzz*)tables);
+            else
+                hipLaunchKernelGGL(k_ecntt_stage, dim3(grid_for(n / 2, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last);
+        }
     }
     {
         ProfScope ps(ctx, "ecntt_normalize", st);

@@ -79,6 +79,12 @@ int bbg_srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, bbg_srs** out);
  * a power of two.  The powers are made on the device and multiplied into G by bbg_g1_fixed_base_mul's kernels (32 n bytes of working
  * memory beside the result, freed before return). */
 int bbg_srs_synth_powers(bbg_ctx* ctx, const uint64_t x[4], size_t n, bbg_srs** out);
+/* The update step of a powers-of-x string: *out is a new SRS of the same length with P_i' = [y^i] P_i (P_0' = P_0), so that a string for x
+ * becomes the string for x y -- what a ceremony participant, or a test harness, does to an EXISTING string whose x nobody knows.  y:
+ * Montgomery Fr on the host, [0, 2r).  y = 0 mod r -> BBG_E_INVALID, *out untouched.  `srs` is only read and must live on the context's
+ * device.  The powers y^i are made on the device and multiplied into the points by bbg_g1_batch_mul_device's kernel (32 n bytes of working
+ * memory beside the result, freed before return, and the tables described there). */
+int bbg_srs_scale_powers(bbg_ctx* ctx, bbg_srs* srs, const uint64_t y[4], bbg_srs** out);
 /* Reads an Ignition-format transcript file (manifest + big-endian points; srs/io.cpp:11-162): result is
  * monomials[0] = G followed by the file's points, num_points in total -- exactly read_transcript_g1. */
 int bbg_srs_load_transcript(bbg_ctx* ctx, const char* path, size_t num_points, bbg_srs** out);
@@ -150,6 +156,22 @@ int bbg_g1_normalize(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t
 int bbg_g1_fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine);
 /* Device-resident: d_scalars and d_out_affine are device pointers, asynchronous on the context stream. */
 int bbg_g1_fixed_base_mul_device(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scalars, size_t n, void* d_out_affine);
+
+/* Variable-base batch scalar multiplication: out_affine[i] = scalars[i] * points_affine[i] for i < n, n different points.  With
+ * one_scalar != 0 only scalars[0] is read and out_affine[i] = scalars[0] * points_affine[i]: element::batch_mul_with_endomorphism(points,
+ * exponent) (ecc/groups/element_impl.hpp:666-832).  points: 64-byte Montgomery affine, any representative in [0, 2p) per coordinate; the
+ * affine encoding of infinity is accepted and gives infinity.  Points are NOT checked to be on the curve: for a point off it the result is
+ * unspecified (but nothing else is affected).  scalars: Montgomery Fr, any representative in [0, 2r).  out: canonical Montgomery affine;
+ * a result at infinity is written exactly as bbg_g1_fixed_base_mul writes it.  n = 0 is legal and does nothing; null pointers with n > 0
+ * are BBG_E_INVALID.  Each product is a GLV multiplication on signed 4-bit windows (csrc/var_base.hip.h: the scalar split against the
+ * cube root of unity into two halves below 2^128, a table of the point's odd multiples P .. 15P, 32 rounds of 4 doublings + 2 additions)
+ * on the complete addition formulas, so every scalar and every point is handled.  Working memory: 1 KiB of table per lane for at most
+ * "batch_mul_lanes" lanes (default 2^17: 128 MiB, whatever n is), counted under `scratch` in bbg_memory_report and released by
+ * bbg_memory_trim.  Timed under "var_base_mul" (bbg_profile_get). */
+int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t* scalars, size_t n, int one_scalar, uint64_t* out_affine);
+/* Device-resident: device pointers, asynchronous on the context stream.  d_out_affine may BE d_points_affine (the points are multiplied
+ * in place); an output that overlaps the points in any other way, or overlaps the scalars, is refused with BBG_E_INVALID. */
+int bbg_g1_batch_mul_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int one_scalar, void* d_out_affine);
 
 /* ---- NTT family: replaces polynomial_arithmetic::fft/ifft/coset_fft/coset_ifft/... on fr* coeffs
  *      (polynomials/polynomial_arithmetic.cpp:374-484) and the C bindings coset_fft_with_generator_shift / ifft
@@ -418,11 +440,14 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
  * "ntt_max_logr8" (6..11, max log-radix per radix-8 pass, default 10), "ntt_big_tile" (0 / 1 / 2: 4096-element tiles for 2^21 [default] / also 2^22),
  * "ntt_lds_planes" (2 = a pass keeps its tile in LDS between two radix-8 steps, 1 = the tile moves one 16-byte plane at a time through half the LDS with
  * three waves per SIMD, 0 = automatic [default]: 1 from 2^22), "prover_msm_batch" (0 .. BBG_MSM_BATCH_MAX, default 4: commitments of a bbg_prover round per
- * launch set; 0 / 1 = one launch set each).
+ * launch set; 0 / 1 = one launch set each),
+ * "batch_mul_glv" (1 = bbg_g1_batch_mul* multiplies with the windowed GLV form, default; 0 = with the bit-serial double-and-add, A/B),
+ * "batch_mul_lanes" (a multiple of 64 in 64 .. 2^20, default 2^17: lanes of the variable-base kernels, each holding a 1 KiB table and walking
+ * the points with that stride), "ecntt_mul" (1 = bbg_srs_lagrange's stages multiply with the windowed GLV form, default; 0 = bit-serially, A/B).
  * Every value of every option gives bit-identical results; they exist for A/B measurements. */
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
- * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul".  enable(…, 1) clears previous samples. */
+ * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
