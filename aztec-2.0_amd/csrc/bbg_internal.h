@@ -22,6 +22,9 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
         if (_e != hipSuccess) return ::bbg::hip_fail(_e, #expr, __FILE__, __LINE__);                                  \
     } while (0)
 
+// blocks of `block` threads that cover n items
+static inline int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
+
 // ---------------------------------------------------------------------------------------------- NTT
 constexpr int NTT_MAX_PASSES = 4;
 

@@ -32,6 +32,16 @@ __device__ __forceinline__ Affine aff_inf()
     r.x.v[7] = 0x80000000u;
     return r;
 }
+// the generator G = (1, 2), Montgomery form, canonical
+__device__ __forceinline__ Affine aff_generator()
+{
+    Affine g;
+    g.x = Fq::one();
+    Fq two = Fq::zero();
+    two.v[0] = 2;
+    g.y = fe_reduce_once(fe_to_mont(two));
+    return g;
+}
 __device__ __forceinline__ Xyzz xyzz_inf()
 {
     Xyzz r;
@@ -227,6 +237,76 @@ __device__ inline Affine xyzz_to_affine(const Xyzz& p)
     r.x = fe_reduce_once(fe_mul(p.x, fe_mul(iz, p.zzz)));
     r.y = fe_reduce_once(fe_mul(p.y, fe_mul(iz, p.zz)));
     return r;
+}
+
+// ---------------------------------------------------------------------------------- batched XYZZ -> canonical affine
+// A thread's chunk of XYZZ points q_0 .. q_(m-1) becomes canonical affine behind ONE inversion (Montgomery's trick over the
+// zw_e = ZZ_e ZZZ_e), without an XYZZ working set.  Every kernel that converts more than one point per thread goes through these three:
+//
+//     Fq run = Fq::one();
+//     for e = 0 .. m-1:    fin[e] = aff_batch_park(q_e, slot_e, zw[e], prefix[e], run);    // ascending
+//     Fq inv = aff_batch_invert(run);
+//     for e = m-1 .. 0:    aff_batch_finish(slot_e, fin[e], zw[e], prefix[e], inv, aff_inf());   // DEscending
+//
+//   * slot_e is the point's own 64-byte place in the output.  Park stores the numerators X ZZZ and Y ZZ there
+//     (x = X / ZZ = X ZZZ / zw, y = Y / ZZZ = Y ZZ / zw); finish reads them back and scales them.  Only zw, the prefix product and the
+//     finite flag of each point stay with the thread.  A thread touches its own slots only, and q_e is complete before slot_e is
+//     written, so a slot may be the place the point was read from.
+//   * Infinite members (ZZ = 0) take no part in the product: zw = 1, nothing is stored, and finish writes `inf_value` (aff_inf(), or
+//     whatever the caller's output format wants) instead.  run is therefore a product of non-zero values and the inversion is defined
+//     for every mix of finite and infinite members, the all-infinite chunk included (run = 1).
+//   * Order: prefix[e] = zw_0 .. zw_(e-1) as park saw it.  On entry to finish for e, inv = 1 / (zw_0 .. zw_e); inv prefix[e] = 1 / zw_e,
+//     and inv zw_e is what e - 1 needs.  Hence ascending parks, descending finishes, and every parked member finished.
+//   * Output: both products are below 2p and go through fe_reduce_once, so the stored words are the canonical representative.
+//   * The parked numerators must be RE-READ from memory by finish, not carried in registers across the 380 products of the inversion:
+//     aff_batch_invert puts a compiler barrier in front of fq_invert.  It is the only way from park to finish.
+__device__ __forceinline__ bool aff_batch_park(const Xyzz& q, Affine* slot, Fq& zw, Fq& prefix, Fq& run)
+{
+    zw = Fq::one();
+    prefix = run;
+    if (xyzz_is_inf(q)) return false;
+    zw = fe_mul(q.zz, q.zzz);
+    Affine s;
+    s.x = fe_mul(q.x, q.zzz);
+    s.y = fe_mul(q.y, q.zz);
+    aff_store(slot, s);
+    run = fe_mul(run, zw);
+    return true;
+}
+__device__ __forceinline__ Fq aff_batch_invert(const Fq& run)
+{
+    asm volatile("" ::: "memory");
+    return fq_invert(run);
+}
+__device__ __forceinline__ void aff_batch_finish(Affine* slot, bool finite, const Fq& zw, const Fq& prefix, Fq& inv, const Affine& inf_value)
+{
+    Affine o = inf_value;
+    if (finite) {
+        const Fq iz = fe_mul(inv, prefix); // 1 / zw of this point
+        inv = fe_mul(inv, zw);
+        const Affine s = aff_load(slot);
+        o.x = fe_reduce_once(fe_mul(s.x, iz));
+        o.y = fe_reduce_once(fe_mul(s.y, iz));
+    }
+    aff_store(slot, o);
+}
+// The same for a chunk of up to four points out[0 .. cnt-1], cnt >= 1, spelt out point by point so that every index is a constant and
+// the four zw, the four prefix products and the flags are registers, not a runtime-indexed array.  produce(e) returns point e; it runs
+// before slot e is written.
+template <class Produce> __device__ __forceinline__ void aff_batch_chunk4(Affine* out, int cnt, Produce produce)
+{
+    Fq zw0, zw1, zw2, zw3, pf0, pf1, pf2, pf3;
+    Fq run = Fq::one();
+    bool f0 = false, f1 = false, f2 = false, f3 = false;
+    f0 = aff_batch_park(produce(0), out, zw0, pf0, run);
+    if (cnt > 1) f1 = aff_batch_park(produce(1), out + 1, zw1, pf1, run);
+    if (cnt > 2) f2 = aff_batch_park(produce(2), out + 2, zw2, pf2, run);
+    if (cnt > 3) f3 = aff_batch_park(produce(3), out + 3, zw3, pf3, run);
+    Fq inv = aff_batch_invert(run);
+    if (cnt > 3) aff_batch_finish(out + 3, f3, zw3, pf3, inv, aff_inf());
+    if (cnt > 2) aff_batch_finish(out + 2, f2, zw2, pf2, inv, aff_inf());
+    if (cnt > 1) aff_batch_finish(out + 1, f1, zw1, pf1, inv, aff_inf());
+    aff_batch_finish(out, f0, zw0, pf0, inv, aff_inf());
 }
 
 } // namespace bbg

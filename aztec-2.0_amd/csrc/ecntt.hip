@@ -19,8 +19,8 @@
 //                      and its A operands are multiplied by n^-1 (n/2 extra scalar multiplications, 1 / log2 n of the work, and no
 //                      pass of its own).  By default (option "ecntt_mul" = 1) the stages run on the windowed GLV multiplication of
 //                      var_base.hip.h instead (k_ecntt_stage_glv: 2.2x at 2^20, profiles/var_base.txt); 0 = this kernel, A/B;
-//   * k_ecntt_normalize  batched conversion to canonical affine, one inversion per NORM_CH points; a point at infinity among the
-//                      outputs raises a flag (an SRS handle never holds one) and the call fails.
+//   * k_ecntt_normalize  batched conversion to canonical affine (aff_batch_*, curve.hip.h), one inversion per NORM_CH points;
+//                      a point at infinity among the outputs raises a flag (an SRS handle never holds one) and the call fails.
 // All group-law cases (equal / opposite operands, infinities inside the transform) are handled by xyzz_add / xyzz_dbl.
 #include "bbg_internal.h"
 #include "curve.hip.h"
@@ -28,8 +28,6 @@
 #include "var_base.hip.h" // xyzz_mul_fr, xyzz_mul_glv, xyzz_neg
 
 namespace bbg {
-
-static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
 __device__ __forceinline__ size_t bit_reverse(size_t i, unsigned bits)
 {
@@ -97,44 +95,29 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __r
     }
 }
 
-// XYZZ -> canonical affine, NORM_CH consecutive points per thread behind one inversion (as k_srs_synth does).  A point at infinity is
-// reported through *inf_flag and stored as the generator, so that whatever is queued behind this kernel still reads valid points; the
-// host discards the result.
+// XYZZ -> canonical affine, NORM_CH consecutive points per thread behind one inversion (the batched conversion of curve.hip.h).  A
+// point at infinity is reported through *inf_flag and stored as the generator, so that whatever is queued behind this kernel still
+// reads valid points; the host discards the result.
 constexpr int NORM_CH = 8;
 __global__ void __launch_bounds__(128) k_ecntt_normalize(const Xyzz* __restrict__ work, Affine* __restrict__ out, size_t n, unsigned* inf_flag)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t i0 = t * NORM_CH;
     if (i0 >= n) return;
-    Fq prod[NORM_CH];
-    Fq acc = Fq::one();
+    // only the prefix products are kept per thread: ZZ ZZZ and the finite flag of a point are taken from `work` again on the way back
+    Fq prefix[NORM_CH];
+    Fq run = Fq::one();
     int cnt = 0;
     bool any_inf = false;
     for (int e = 0; e < NORM_CH && i0 + e < n; e++) {
-        const Fq zz = fe_load<FqP>(&work[i0 + e].zz), zzz = fe_load<FqP>(&work[i0 + e].zzz);
-        prod[e] = acc;
-        if (zz.is_zero_raw())
-            any_inf = true;
-        else
-            acc = fe_mul(acc, fe_mul(zz, zzz));
+        Fq zw;
+        any_inf |= !aff_batch_park(xyzz_load(work + i0 + e), out + i0 + e, zw, prefix[e], run);
         cnt++;
     }
-    Fq inv = fq_invert(acc);
+    Fq inv = aff_batch_invert(run);
     for (int e = cnt - 1; e >= 0; e--) {
-        const Xyzz p = xyzz_load(work + i0 + e);
-        Affine o;
-        if (xyzz_is_inf(p)) {
-            o.x = Fq::one();
-            Fq two = Fq::zero();
-            two.v[0] = 2;
-            o.y = fe_reduce_once(fe_to_mont(two));
-        } else {
-            const Fq iz = fe_mul(inv, prod[e]);
-            inv = fe_mul(inv, fe_mul(p.zz, p.zzz));
-            o.x = fe_reduce_once(fe_mul(p.x, fe_mul(iz, p.zzz)));
-            o.y = fe_reduce_once(fe_mul(p.y, fe_mul(iz, p.zz)));
-        }
-        aff_store(out + i0 + e, o);
+        const Fq zz = fe_load<FqP>(&work[i0 + e].zz), zzz = fe_load<FqP>(&work[i0 + e].zzz);
+        aff_batch_finish(out + i0 + e, !zz.is_zero_raw(), fe_mul(zz, zzz), prefix[e], inv, aff_generator());
     }
     if (any_inf) atomicOr(inf_flag, 1u);
 }

@@ -12,8 +12,7 @@
 //                  sum_w T[w][d_w - 1] -- at most 32 complete mixed additions (xyzz_madd) and NO doubling.  The scalar is shifted right
 //                  one byte per step so that the digit is always the low byte of limb 0: no runtime-indexed limb, the loop body exists
 //                  once, and the table entry of the NEXT digit is loaded before the current addition starts.  The FB_CH results are made
-//                  affine behind one inversion: X*ZZZ and Y*ZZ are parked in the point's own 64-byte output slot, ZZ*ZZZ and the prefix
-//                  products stay in registers, and after the inversion the slot is read back and scaled.  A result at infinity
+//                  affine behind one inversion by the batched conversion of curve.hip.h (aff_batch_*).  A result at infinity
 //                  (s = 0 mod r, or an infinite base) is written as aff_inf().
 //   * k_fb_powers  s_i = x^i for the structured string (each thread starts its run of FB_POW_E powers with a square-and-multiply).
 // All group-law cases are handled by xyzz_madd / xyzz_add / xyzz_dbl, although with a canonical scalar k < r the accumulator
@@ -24,8 +23,6 @@
 #include <cstring>
 
 namespace bbg {
-
-static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
 constexpr int FB_WINDOWS = 32;  // byte positions of a 256-bit scalar
 constexpr int FB_DIGITS = 255;  // entries per window: d = 1 .. 255 (d = 0 adds nothing)
@@ -90,60 +87,18 @@ __device__ __forceinline__ Xyzz fb_mul_one(const Affine* __restrict__ table, Fr 
     return acc;
 }
 
-// Forward half of one point of a thread's chunk: q = k B, its numerators X ZZZ and Y ZZ parked in the output slot, zw = ZZ ZZZ joins the
-// running product.  Returns false for a result at infinity (zw stays one).
-__device__ __forceinline__ bool fb_forward(const Affine* __restrict__ table, const Fr* __restrict__ scalar, Affine* slot, Fq& zw, Fq& prefix, Fq& run)
-{
-    zw = Fq::one();
-    prefix = run;
-    const Xyzz q = fb_mul_one(table, fe_from_mont(fe_load<FrP>(scalar)));
-    if (xyzz_is_inf(q)) return false;
-    zw = fe_mul(q.zz, q.zzz);
-    Affine s;
-    s.x = fe_mul(q.x, q.zzz); // x = X / ZZ  = X ZZZ / (ZZ ZZZ)
-    s.y = fe_mul(q.y, q.zz);  // y = Y / ZZZ = Y ZZ  / (ZZ ZZZ)
-    aff_store(slot, s);
-    run = fe_mul(run, zw);
-    return true;
-}
-// Backward half: inv = 1 / (zw_0 .. zw_e) on entry, 1 / (zw_0 .. zw_(e-1)) on return
-__device__ __forceinline__ void fb_backward(Affine* slot, bool finite, const Fq& zw, const Fq& prefix, Fq& inv)
-{
-    Affine o = aff_inf();
-    if (finite) {
-        const Fq iz = fe_mul(inv, prefix); // 1 / (ZZ ZZZ) of this point
-        inv = fe_mul(inv, zw);
-        const Affine s = aff_load(slot);
-        o.x = fe_reduce_once(fe_mul(s.x, iz));
-        o.y = fe_reduce_once(fe_mul(s.y, iz));
-    }
-    aff_store(slot, o);
-}
-
-// Two waves per SIMD; no scratch, no LDS.  The chunk is written out point by point (FB_CH = 4) so that every register array index is a
-// constant.
+// Two waves per SIMD; no scratch, no LDS.  The FB_CH results of a thread become canonical affine behind one inversion (aff_batch_chunk4,
+// curve.hip.h); a result at infinity is written as aff_inf().
 // Scalars arrive in Montgomery form as any 256-bit representative a: fe_from_mont returns reduce_once((a + m p) / 2^256) with m < 2^256,
 // and (a + m p) / 2^256 < 1 + p, so the plain value is canonical (k < r) whatever representative came in.
-static_assert(FB_CH == 4, "k_fb_mul spells its chunk out");
+static_assert(FB_CH == 4, "k_fb_mul converts its chunk with aff_batch_chunk4");
 __global__ void __launch_bounds__(64, 2) k_fb_mul(const Affine* __restrict__ table, const Fr* __restrict__ scalars, size_t n, Affine* out)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t i0 = t * FB_CH;
     if (i0 >= n) return;
     const int cnt = n - i0 < (size_t)FB_CH ? (int)(n - i0) : FB_CH;
-    Fq zw0, zw1, zw2, zw3, pf0, pf1, pf2, pf3;
-    Fq run = Fq::one();
-    bool f0 = false, f1 = false, f2 = false, f3 = false;
-    f0 = fb_forward(table, scalars + i0, out + i0, zw0, pf0, run);
-    if (cnt > 1) f1 = fb_forward(table, scalars + i0 + 1, out + i0 + 1, zw1, pf1, run);
-    if (cnt > 2) f2 = fb_forward(table, scalars + i0 + 2, out + i0 + 2, zw2, pf2, run);
-    if (cnt > 3) f3 = fb_forward(table, scalars + i0 + 3, out + i0 + 3, zw3, pf3, run);
-    asm volatile("" ::: "memory"); // the parked numerators are re-read from memory below, not kept in registers across the inversion
-    Fq inv = fq_invert(run);
-    if (cnt > 3) fb_backward(out + i0 + 3, f3, zw3, pf3, inv);
-    if (cnt > 2) fb_backward(out + i0 + 2, f2, zw2, pf2, inv);
-    if (cnt > 1) fb_backward(out + i0 + 1, f1, zw1, pf1, inv);
-    fb_backward(out + i0, f0, zw0, pf0, inv);
+    aff_batch_chunk4(out + i0, cnt, [&](int e) __attribute__((always_inline)) { return fb_mul_one(table, fe_from_mont(fe_load<FrP>(scalars + i0 + e))); });
 }
 
 // ---------------------------------------------------------------------------------------------- powers

@@ -33,11 +33,9 @@
 
 namespace bbg {
 
-static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
-
 // ---------------------------------------------------------------------------------- synthetic SRS
 // P_i = (a + i*s) * G : thread t owns CH consecutive points; start by double-and-add, then madd steps, normalise
-// with one inversion per thread.
+// with one inversion per thread (the batched conversion of curve.hip.h: the numerators wait in the output slots).
 constexpr int SYNTH_CH = 16;
 __device__ Xyzz g1_mul_u128(const Affine& g, unsigned __int128 k)
 {
@@ -54,33 +52,20 @@ __global__ void __launch_bounds__(128) k_srs_synth(Affine* out, size_t n, uint64
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t i0 = t * SYNTH_CH;
     if (i0 >= n) return;
-    Affine G;
-    G.x = Fq::one();
-    Fq two = Fq::zero();
-    two.v[0] = 2;
-    G.y = fe_reduce_once(fe_to_mont(two));
+    const Affine G = aff_generator();
     Affine S = xyzz_to_affine(g1_mul_u64(G, s));
     Xyzz q = g1_mul_u128(G, (unsigned __int128)a + (unsigned __int128)i0 * s); // no 64-bit wrap: P_i = (a + i*s) G over the integers
-    Xyzz pts[SYNTH_CH];
-    Fq prod[SYNTH_CH];
-    Fq acc = Fq::one();
+    Fq zw[SYNTH_CH], prefix[SYNTH_CH];
+    bool fin[SYNTH_CH];
+    Fq run = Fq::one();
     int cnt = 0;
     for (int e = 0; e < SYNTH_CH && i0 + e < n; e++) {
-        pts[e] = q;
-        prod[e] = acc;
-        acc = fe_mul(acc, fe_mul(q.zz, q.zzz));
+        fin[e] = aff_batch_park(q, out + i0 + e, zw[e], prefix[e], run);
         q = xyzz_madd(q, S);
         cnt++;
     }
-    Fq inv = fq_invert(acc);
-    for (int e = cnt - 1; e >= 0; e--) {
-        Fq iz = fe_mul(inv, prod[e]);
-        inv = fe_mul(inv, fe_mul(pts[e].zz, pts[e].zzz));
-        Affine o;
-        o.x = fe_reduce_once(fe_mul(pts[e].x, fe_mul(iz, pts[e].zzz)));
-        o.y = fe_reduce_once(fe_mul(pts[e].y, fe_mul(iz, pts[e].zz)));
-        aff_store(out + i0 + e, o);
-    }
+    Fq inv = aff_batch_invert(run);
+    for (int e = cnt - 1; e >= 0; e--) aff_batch_finish(out + i0 + e, fin[e], zw[e], prefix[e], inv, aff_inf());
 }
 
 // P_i = k_i * G with k_i = mix64(seed + i) | 1: a synthetic SRS without small linear relations (the A + i*S
@@ -98,31 +83,17 @@ __global__ void __launch_bounds__(128) k_srs_hashed(Affine* out, size_t n, uint6
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t i0 = t * HASH_CH;
     if (i0 >= n) return;
-    Affine G;
-    G.x = Fq::one();
-    Fq two = Fq::zero();
-    two.v[0] = 2;
-    G.y = fe_reduce_once(fe_to_mont(two));
-    Xyzz pts[HASH_CH];
-    Fq prod[HASH_CH];
-    Fq acc = Fq::one();
+    const Affine G = aff_generator();
+    Fq zw[HASH_CH], prefix[HASH_CH];
+    bool fin[HASH_CH];
+    Fq run = Fq::one();
     int cnt = 0;
     for (int e = 0; e < HASH_CH && i0 + e < n; e++) {
-        Xyzz q = g1_mul_u64(G, mix64(seed + (uint64_t)(i0 + e)) | 1ULL);
-        pts[e] = q;
-        prod[e] = acc;
-        acc = fe_mul(acc, fe_mul(q.zz, q.zzz));
+        fin[e] = aff_batch_park(g1_mul_u64(G, mix64(seed + (uint64_t)(i0 + e)) | 1ULL), out + i0 + e, zw[e], prefix[e], run);
         cnt++;
     }
-    Fq inv = fq_invert(acc);
-    for (int e = cnt - 1; e >= 0; e--) {
-        Fq iz = fe_mul(inv, prod[e]);
-        inv = fe_mul(inv, fe_mul(pts[e].zz, pts[e].zzz));
-        Affine o;
-        o.x = fe_reduce_once(fe_mul(pts[e].x, fe_mul(iz, pts[e].zzz)));
-        o.y = fe_reduce_once(fe_mul(pts[e].y, fe_mul(iz, pts[e].zz)));
-        aff_store(out + i0 + e, o);
-    }
+    Fq inv = aff_batch_invert(run);
+    for (int e = cnt - 1; e >= 0; e--) aff_batch_finish(out + i0 + e, fin[e], zw[e], prefix[e], inv, aff_inf());
 }
 
 // ---------------------------------------------------------------------------------- last reduce stage, g1 helpers

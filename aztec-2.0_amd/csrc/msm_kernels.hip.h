@@ -15,11 +15,9 @@
 
 namespace bbg {
 
-static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
-
 // ---------------------------------------------------------------------------------- SRS precomputation
 // table[w * n + i] = 2^(table_offset(w)) * P_i (affine, canonical).  One thread per point: doublings in XYZZ from one window to
-// the next, then one shared inversion (Montgomery's trick over the Z-products) to normalise.
+// the next, each multiple parked in its own table slot, then one shared inversion to normalise (the batched conversion of curve.hip.h).
 template <int C> __global__ void __launch_bounds__(128) k_precompute_tables(const Affine* __restrict__ points, Affine* table, size_t n)
 {
     using K = MsmCfg<C>;
@@ -34,28 +32,17 @@ template <int C> __global__ void __launch_bounds__(128) k_precompute_tables(cons
     p.x = fe_reduce_once(p.x);
     p.y = fe_reduce_once(p.y);
     aff_store(table + i, p);
-    // the multiples live in per-thread scratch (one-off kernel: simplicity over registers)
-    Xyzz pts[MSM_WINDOWS - 1];
-    Fq prod[MSM_WINDOWS - 1];
+    Fq zw[MSM_WINDOWS - 1], prefix[MSM_WINDOWS - 1];
+    bool fin[MSM_WINDOWS - 1];
     Xyzz q = xyzz_dbl_affine(p); // 2^1 P
     int at = 1;
-    Fq acc = Fq::one();
+    Fq run = Fq::one();
     for (int w = 1; w < MSM_WINDOWS; w++) {
         for (; at < K::table_offset(w); at++) q = xyzz_dbl(q);
-        pts[w - 1] = q;
-        prod[w - 1] = acc;
-        acc = fe_mul(acc, fe_mul(q.zz, q.zzz));
+        fin[w - 1] = aff_batch_park(q, table + (size_t)w * n + i, zw[w - 1], prefix[w - 1], run);
     }
-    Fq inv = fq_invert(acc);
-    for (int w = MSM_WINDOWS - 1; w >= 1; w--) {
-        const Xyzz& t = pts[w - 1];
-        Fq iz = fe_mul(inv, prod[w - 1]); // 1 / (ZZ * ZZZ) of point w
-        inv = fe_mul(inv, fe_mul(t.zz, t.zzz));
-        Affine a;
-        a.x = fe_reduce_once(fe_mul(t.x, fe_mul(iz, t.zzz))); // X / ZZ
-        a.y = fe_reduce_once(fe_mul(t.y, fe_mul(iz, t.zz)));  // Y / ZZZ
-        aff_store(table + (size_t)w * n + i, a);
-    }
+    Fq inv = aff_batch_invert(run);
+    for (int w = MSM_WINDOWS - 1; w >= 1; w--) aff_batch_finish(table + (size_t)w * n + i, fin[w - 1], zw[w - 1], prefix[w - 1], inv, aff_inf());
 }
 
 // ---------------------------------------------------------------------------------- scalar recoding

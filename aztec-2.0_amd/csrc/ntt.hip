@@ -410,8 +410,6 @@ __global__ void k_to_rprime(uint32_t* out, const Fr* in, size_t count, int shoup
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
-
 // sizes at which the 29-bit-limb pass kernel is the automatic choice (option ntt_limbs29 = -1).  Measured, isolated fft, ms
 // (profiles/r04_ntt29_ab.txt, last series; best 32-bit kernel -> k_ntt_pass29): 2^16 0.0523 -> 0.0507, 2^19 0.0773 -> 0.0748,
 // 2^20 0.1225 -> 0.1107, 2^21 0.2540 -> 0.2329, 2^22 0.4788 -> 0.4447, 2^23 0.9477 -> 0.8851, 2^24 1.9194 -> 1.7706.

@@ -12,8 +12,6 @@
 
 namespace bbg {
 
-static int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
-
 // ---------------------------------------------------------------------------------------------- pointwise
 template <int OP> __global__ void __launch_bounds__(256) k_poly_binop(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr* r, size_t n)
 {

@@ -156,7 +156,6 @@ int commit(bbg_prover* p, int count, const void* const* d_polys, const size_t* l
     p->ctx->msm_window = saved_window;
     return rc;
 }
-int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
 // the MSMs of a round keep their reduce phase on the auxiliary stream; RAII so that every exit path restores the option
 struct AsyncReduce {

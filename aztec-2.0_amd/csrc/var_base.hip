@@ -7,8 +7,8 @@
 //                     lane count (option "batch_mul_lanes", default 2^17 = two waves on every SIMD: 128 MiB), whatever n is.  Per point:
 //                     the scalar out of Montgomery form, then xyzz_mul_glv (GLV = true: 128 doublings + 74 additions) or the bit-serial
 //                     xyzz_mul_fr (GLV = false: 256 + ~127; option "batch_mul_glv" = 0, A/B -- it needs no table).  The VB_CH results become
-//                     canonical affine behind one inversion exactly as in k_fb_mul (fixed_base.hip): X ZZZ and Y ZZ are parked in the point's
-//                     own output slot, ZZ ZZZ and the prefix products stay in registers.  An infinite result is written as aff_inf().
+//                     canonical affine behind one inversion by the batched conversion of curve.hip.h (aff_batch_*).  An infinite result
+//                     is written as aff_inf().
 // A lane reads point i before it writes slot i and touches no other lane's slots, so d_out may BE d_points (in place).
 #include "bbg_internal.h"
 #include "var_base.hip.h"
@@ -24,41 +24,10 @@ template <bool GLV> __device__ __forceinline__ Xyzz vb_mul_one(const Affine& p, 
     return xyzz_mul_fr(xyzz_from_affine(p), k);
 }
 
-// Forward half of one point of a lane's chunk: q = k P, its numerators X ZZZ and Y ZZ parked in the output slot, zw = ZZ ZZZ joins the
-// running product.  Returns false for a result at infinity (zw stays one).
-template <bool GLV>
-__device__ __forceinline__ bool vb_forward(const Affine* point, const Fr* __restrict__ scalar, Affine* slot, Xyzz* table, Fq& zw, Fq& prefix, Fq& run)
-{
-    zw = Fq::one();
-    prefix = run;
-    const Xyzz q = vb_mul_one<GLV>(aff_load(point), fe_from_mont(fe_load<FrP>(scalar)), table);
-    if (xyzz_is_inf(q)) return false;
-    zw = fe_mul(q.zz, q.zzz);
-    Affine s;
-    s.x = fe_mul(q.x, q.zzz); // x = X / ZZ  = X ZZZ / (ZZ ZZZ)
-    s.y = fe_mul(q.y, q.zz);  // y = Y / ZZZ = Y ZZ  / (ZZ ZZZ)
-    aff_store(slot, s);
-    run = fe_mul(run, zw);
-    return true;
-}
-// Backward half: inv = 1 / (zw_0 .. zw_e) on entry, 1 / (zw_0 .. zw_(e-1)) on return
-__device__ __forceinline__ void vb_backward(Affine* slot, bool finite, const Fq& zw, const Fq& prefix, Fq& inv)
-{
-    Affine o = aff_inf();
-    if (finite) {
-        const Fq iz = fe_mul(inv, prefix); // 1 / (ZZ ZZZ) of this point
-        inv = fe_mul(inv, zw);
-        const Affine s = aff_load(slot);
-        o.x = fe_reduce_once(fe_mul(s.x, iz));
-        o.y = fe_reduce_once(fe_mul(s.y, iz));
-    }
-    aff_store(slot, o);
-}
-
-// Two waves per SIMD; the chunk is written out point by point (VB_CH = 4) so that every register array index is a constant.
+// Two waves per SIMD.  The VB_CH results of a chunk become canonical affine behind one inversion (aff_batch_chunk4, curve.hip.h), which
+// asks for point e before it writes slot e: points and out carry no __restrict__, they may be the same buffer.
 // Scalars arrive in Montgomery form as any representative in [0, 2r): fe_from_mont returns the canonical plain value (fixed_base.hip).
-// points and out carry no __restrict__: they may be the same buffer.
-static_assert(VB_CH == 4, "k_vb_mul spells its chunk out");
+static_assert(VB_CH == 4, "k_vb_mul converts its chunk with aff_batch_chunk4");
 template <bool GLV>
 __global__ void __launch_bounds__(64, 2) k_vb_mul(const Affine* points, const Fr* __restrict__ scalars, size_t n, int one_scalar, Affine* out, Xyzz* tables)
 {
@@ -72,19 +41,7 @@ __global__ void __launch_bounds__(64, 2) k_vb_mul(const Affine* points, const Fr
         const int cnt = n - i0 < (size_t)VB_CH ? (int)(n - i0) : VB_CH;
         const Fr* s0 = scalars + (one_scalar ? 0 : i0);
         const size_t ss = one_scalar ? 0 : 1;
-        Fq zw0, zw1, zw2, zw3, pf0, pf1, pf2, pf3;
-        Fq run = Fq::one();
-        bool f0 = false, f1 = false, f2 = false, f3 = false;
-        f0 = vb_forward<GLV>(points + i0, s0, out + i0, table, zw0, pf0, run);
-        if (cnt > 1) f1 = vb_forward<GLV>(points + i0 + 1, s0 + ss, out + i0 + 1, table, zw1, pf1, run);
-        if (cnt > 2) f2 = vb_forward<GLV>(points + i0 + 2, s0 + 2 * ss, out + i0 + 2, table, zw2, pf2, run);
-        if (cnt > 3) f3 = vb_forward<GLV>(points + i0 + 3, s0 + 3 * ss, out + i0 + 3, table, zw3, pf3, run);
-        asm volatile("" ::: "memory"); // the parked numerators are re-read from memory below, not kept in registers across the inversion
-        Fq inv = fq_invert(run);
-        if (cnt > 3) vb_backward(out + i0 + 3, f3, zw3, pf3, inv);
-        if (cnt > 2) vb_backward(out + i0 + 2, f2, zw2, pf2, inv);
-        if (cnt > 1) vb_backward(out + i0 + 1, f1, zw1, pf1, inv);
-        vb_backward(out + i0, f0, zw0, pf0, inv);
+        aff_batch_chunk4(out + i0, cnt, [&](int e) __attribute__((always_inline)) { return vb_mul_one<GLV>(aff_load(points + i0 + e), fe_from_mont(fe_load<FrP>(s0 + e * ss)), table); });
     }
 }
 
