@@ -52,7 +52,8 @@ int bbg_sync(bbg_ctx* ctx);
  * bbg_join(): it makes the context stream wait (on the device, no host sync) for all outstanding reductions. */
 int bbg_join(bbg_ctx* ctx);
 /* Like bbg_join but leaves the `lag` most recent reductions outstanding (lag = 1: wait for everything except the
- * MSM issued last) -- lets a caller consume result i-1 while MSM i is still reducing. */
+ * MSM issued last) -- lets a caller consume result i-1 while MSM i is still reducing.  At most two reductions are ever
+ * outstanding (the reduce slots; a third MSM waits for the slot it reuses), so lag >= 2 waits for nothing and returns BBG_OK. */
 int bbg_join_lag(bbg_ctx* ctx, int lag);
 /* Use a caller-owned HIP stream (hipStream_t passed as void*; e.g. torch.cuda.current_stream().cuda_stream).  Every *_device
  * entry point enqueues on the context stream and returns; a caller that fills or reads those device buffers on ANOTHER stream

@@ -711,7 +711,9 @@ def test_msm_wide_windows_vs_oracle(pkg, oracle, bbg, golden, srs16, window):
 def test_msm_async_reduce_with_changing_shapes(pkg, oracle, bbg, srs16):
     """msm_async_reduce = 1 queues each MSM's bucket reduction on an auxiliary stream with double-buffered slots.  Back-to-back
     MSMs of DIFFERENT sizes / window widths re-lay-out the scratch arena, so the library must join the pending reductions
-    first: every result of an interleaved sequence must equal the synchronous one."""
+    first: every result of an interleaved sequence must equal the synchronous one.  The bbg.sync() behind its join() waits for the
+    auxiliary reduce streams as well, so this test cannot see a missing join: the stream-ordered check of join() / join(lag) lives in
+    tests/test_gpu_stream_order.py."""
     import torch
     sizes = [1 << 16, 1000, 1 << 15, 17, 40001, 1 << 16, 3]
     windows = [16, 20, 17, 16, 22, 19, 16]
