@@ -108,6 +108,10 @@ def load_library():
         "bbg_poly_evaluate_device": (cint, [vp, vp, sz, vp, vp]),
         "bbg_kate_opening_device": (cint, [vp, vp, vp, sz, vp, vp]),
         "bbg_divide_by_pseudo_vanishing_device": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz]),
+        "bbg_fr_batch_invert_device": (cint, [vp, vp, vp, sz]),
+        "bbg_poly_evaluate_lagrange_device": (cint, [vp, vp, vp, sz, ctypes.c_uint, vp, vp]),
+        "bbg_poly_evaluate_lagrange": (cint, [vp, vp, ctypes.c_uint, vp, vp]),
+        "bbg_kate_opening_lagrange_device": (cint, [vp, vp, vp, ctypes.c_uint, vp, vp]),
         "bbg_dev_alloc": (cint, [vp, sz, ctypes.POINTER(vp)]),
         "bbg_dev_free": (cint, [vp, vp]),
         "bbg_dev_upload": (cint, [vp, vp, vp, sz]),
@@ -125,6 +129,7 @@ def load_library():
         "bbg_prover_round3": (cint, [vp, vp, vp, vp, vp]),
         "bbg_prover_round4": (cint, [vp, vp, vp, vp]),
         "bbg_prover_evaluate": (cint, [vp, sz, vp, vp, vp, vp]),
+        "bbg_prover_evaluate_lagrange": (cint, [vp, sz, vp, vp, vp, vp]),
         "bbg_prover_linearise": (cint, [vp, sz, vp, vp, vp, vp]),
         "bbg_prover_round6": (cint, [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         "bbg_prover_read_poly": (cint, [vp, cint, cint, vp, sz]),
@@ -165,6 +170,8 @@ EXPORTED_SYMBOLS = [
     "bbg_multi_srs_synth_hashed", "bbg_multi_srs_num_points", "bbg_multi_msm", "bbg_multi_ntt_device", "bbg_multi_ntt", "bbg_multi_set_option",
     "bbg_g1_fixed_base_mul", "bbg_g1_fixed_base_mul_device", "bbg_srs_synth_powers",
     "bbg_g1_batch_mul", "bbg_g1_batch_mul_device", "bbg_srs_scale_powers",
+    "bbg_fr_batch_invert_device", "bbg_poly_evaluate_lagrange_device", "bbg_poly_evaluate_lagrange", "bbg_kate_opening_lagrange_device",
+    "bbg_prover_evaluate_lagrange",
 ]
 
 
@@ -490,6 +497,41 @@ class Bbg:
         out = np.zeros(4, dtype=np.uint64)
         self._ck(self.lib.bbg_kate_opening_device(self.ctx, ctypes.c_void_p(d_src), ctypes.c_void_p(d_dest), n, zz.ctypes.data,
                                                   out.ctypes.data))
+        return out
+
+    # ---- Lagrange form: values on the 2^log2n domain instead of coefficients (csrc/barycentric.hip)
+    def fr_batch_invert_device(self, d_in, d_out, n):
+        """out[i] = in[i]^-1, zero stays zero; d_out may be d_in.  Asynchronous."""
+        self._ck(self.lib.bbg_fr_batch_invert_device(self.ctx, ctypes.c_void_p(d_in), ctypes.c_void_p(d_out), n))
+
+    def poly_evaluate_lagrange_device(self, d_evals, log2n, z, shifted=None):
+        """F_k(z), or F_k(z * w) where shifted[k], for the device arrays d_evals[k] of 2^log2n values: (count, 4) canonical words."""
+        count = len(d_evals)
+        arr = (ctypes.c_void_p * max(count, 1))(*[ctypes.c_void_p(int(p)) for p in d_evals])
+        sh = None if shifted is None else (ctypes.c_int * max(count, 1))(*[int(bool(x)) for x in shifted])
+        zz = np.ascontiguousarray(z, dtype=np.uint64)
+        out = np.zeros((max(count, 1), 4), dtype=np.uint64)
+        self._ck(self.lib.bbg_poly_evaluate_lagrange_device(self.ctx, arr, sh, count, log2n, zz.ctypes.data, out.ctypes.data))
+        return out[:count]
+
+    def poly_evaluate_lagrange(self, evals, z):
+        """Host-buffer form for one polynomial of 2^k values."""
+        a = _u64(evals, 4)
+        n = a.shape[0]
+        log2n = n.bit_length() - 1
+        if n == 0 or (1 << log2n) != n:
+            raise ValueError("value count must be a power of two")
+        zz = np.ascontiguousarray(z, dtype=np.uint64)
+        out = np.zeros(4, dtype=np.uint64)
+        self._ck(self.lib.bbg_poly_evaluate_lagrange(self.ctx, a.ctypes.data, log2n, zz.ctypes.data, out.ctypes.data))
+        return out
+
+    def kate_opening_lagrange_device(self, d_evals, d_dest, log2n, z):
+        """d_dest = the values of (F(X) - F(z)) / (X - z) on the domain; returns F(z)."""
+        zz = np.ascontiguousarray(z, dtype=np.uint64)
+        out = np.zeros(4, dtype=np.uint64)
+        self._ck(self.lib.bbg_kate_opening_lagrange_device(self.ctx, ctypes.c_void_p(d_evals), ctypes.c_void_p(d_dest), log2n, zz.ctypes.data,
+                                                           out.ctypes.data))
         return out
 
     # host-buffer forms (what the C++ shim binds evaluate / compute_kate_opening_coefficients / divide_by_pseudo_vanishing_polynomial to)

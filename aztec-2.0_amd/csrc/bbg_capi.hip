@@ -1286,6 +1286,37 @@ int bbg_kate_opening(bbg_ctx* ctx, const uint64_t* src, uint64_t* dest, size_t n
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
+int bbg_fr_batch_invert_device(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return poly_batch_invert(ctx, d_in, d_out, n, ctx->stream);
+}
+int bbg_poly_evaluate_lagrange_device(bbg_ctx* ctx, const void* const* d_evals, const int* shifted, size_t count, unsigned log2n, const uint64_t z[4],
+                                      uint64_t* out)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return poly_evaluate_lagrange(ctx, d_evals, shifted, count, log2n, z, out, ctx->stream);
+}
+int bbg_poly_evaluate_lagrange(bbg_ctx* ctx, const uint64_t* evals, unsigned log2n, const uint64_t z[4], uint64_t out[4])
+{
+    CHECK_CTX(ctx);
+    if (!evals || !z || !out || log2n == 0 || log2n > 28) { set_error("bbg_poly_evaluate_lagrange: bad argument (1 <= log2n <= 28)"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t bytes = ((size_t)1 << log2n) * 32;
+    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, bytes);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(ctx->staging, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const void* d_evals = ctx->staging;
+    return poly_evaluate_lagrange(ctx, &d_evals, nullptr, 1, log2n, z, out, ctx->stream);
+}
+int bbg_kate_opening_lagrange_device(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t z[4], uint64_t f_out[4])
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return poly_kate_opening_lagrange(ctx, d_evals, d_dest, log2n, z, f_out, ctx->stream);
+}
 int bbg_divide_by_pseudo_vanishing(bbg_ctx* ctx, uint64_t* evals, unsigned log2_src, unsigned log2_target, size_t num_roots_cut)
 {
     CHECK_CTX(ctx);

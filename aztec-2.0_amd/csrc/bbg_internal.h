@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -215,6 +216,38 @@ int poly_binop(int op, const void* a, const void* b, void* r, size_t n, hipStrea
 int poly_evaluate(bbg_ctx* ctx, const void* d_coeffs, size_t n, const uint64_t* z, uint64_t* out, hipStream_t st);
 int poly_kate_opening(bbg_ctx* ctx, const void* d_src, void* d_dest, size_t n, const uint64_t* z, uint64_t* f_out, hipStream_t st);
 int poly_divide_pseudo_vanishing(bbg_ctx* ctx, void* d_evals, unsigned log2_src, unsigned log2_target, size_t roots_cut, hipStream_t st);
+// barycentric.hip / poly.hip: polynomials in Lagrange form (values on the 2^log2n domain).  BARY_E values per thread, lane-interleaved;
+// one 256-thread block covers BARY_BLK consecutive domain points, which is also the group of ONE inversion (Montgomery's trick)
+#ifndef BBG_BARY_E
+#define BBG_BARY_E 4 // A/B builds only: make EXTRA=-DBBG_BARY_E=8
+#endif
+constexpr int BARY_E = BBG_BARY_E, BARY_BLK = 256 * BARY_E, BARY_MAX = 32;
+constexpr size_t BARY_GRID_MAX = 1024; // four blocks per CU; longer arrays go round a grid-stride loop
+constexpr unsigned BARY_NO_HIT = 0xffffffffu;
+static inline unsigned bary_grid(size_t n) { return (unsigned)std::min((n + BARY_BLK - 1) / BARY_BLK, BARY_GRID_MAX); }
+struct BaryArgs {
+    const void* polys[BARY_MAX]; // device arrays of 2^log2n values
+    uint32_t shifted;            // bit k: polynomial k at z * w instead of z
+    int count;
+    unsigned log2n;
+    uint32_t z[8], zn[8]; // canonical Montgomery words of z and z^n
+    const void* consts;   // DomainConsts of the domain
+    void* dest;           // opening only: 2^log2n values, else null
+    void* partials;       // count x bary_grid(n) values
+    void* results;        // count values
+    unsigned* flag;
+};
+// out[i] = in[i]^-1 (zero stays zero), canonical; d_out may be d_in.  Queues only.
+int bary_batch_invert(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n, hipStream_t st);
+// results[k] = F_k(z) or F_k(z w); with dest, dest = the values of (F_0(X) - F_0(z)) / (X - z) as well (count = 1).  Queues only.
+int bary_evaluate(bbg_ctx* ctx, const BaryArgs& a, hipStream_t st);
+// poly.hip: the host side.  *d_results: count canonical values on the device (context scratch), valid until the next polynomial call.
+int poly_evaluate_lagrange_async(bbg_ctx* ctx, const void* const* d_evals, const int* shifted, size_t count, unsigned log2n, const uint64_t* z,
+                                 void* d_dest, void** d_results, hipStream_t st);
+int poly_evaluate_lagrange(bbg_ctx* ctx, const void* const* d_evals, const int* shifted, size_t count, unsigned log2n, const uint64_t* z, uint64_t* out,
+                           hipStream_t st);
+int poly_kate_opening_lagrange(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t* z, uint64_t* f_out, hipStream_t st);
+int poly_batch_invert(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n, hipStream_t st);
 // the divisor as a per-point table (cached per context); *table stays valid until bbg_memory_trim / bbg_destroy
 int poly_dpv_table(bbg_ctx* ctx, unsigned log2_src, unsigned log2_target, size_t roots_cut, const void** table, hipStream_t st);
 int ntt_scale_powers(bbg_ctx* ctx, void* d_a, size_t count, const uint64_t* start, const uint64_t* base, hipStream_t stream);

@@ -82,6 +82,7 @@ struct DpvConsts {
 struct PolyHeader {
     PolyScratch ps[2];
     Fr results[MEV_MAX];
+    unsigned bary_flag; // barycentric evaluation: the index i of a zero z w^-i - 1, BARY_NO_HIT otherwise (reset by every call)
 };
 static int poly_scratch(bbg_ctx* ctx, size_t partials, PolyHeader** hdr, Fr** part)
 {
@@ -538,6 +539,91 @@ int poly_kate_opening(bbg_ctx* ctx, const void* d_src, void* d_dest, size_t n, c
     int rc = poly_kate_opening_async(ctx, d_src, d_dest, n, z, nullptr, st);
     if (rc) return rc;
     BBG_HIP(hipMemcpyAsync(f_out, &((PolyHeader*)ctx->poly_scratch)->ps[0].result, 32, hipMemcpyDeviceToHost, st));
+    BBG_HIP(hipStreamSynchronize(st));
+    return BBG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Lagrange form (kernels: barycentric.hip)
+static bool ranges_overlap(const void* a, const void* b, size_t bytes)
+{
+    const char *x = (const char*)a, *y = (const char*)b;
+    return x < y + bytes && y < x + bytes;
+}
+int poly_batch_invert(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n, hipStream_t st)
+{
+    if (!d_in || !d_out) { set_error("bbg_fr_batch_invert_device: null argument"); return BBG_E_INVALID; }
+    if (n == 0) return BBG_OK;
+    if (d_in != d_out && ranges_overlap(d_in, d_out, n * 32)) {
+        set_error("bbg_fr_batch_invert_device: the output overlaps the input without being the same buffer");
+        return BBG_E_INVALID;
+    }
+    return bary_batch_invert(ctx, d_in, d_out, n, st);
+}
+// z^n of the canonical z, canonical (host_pow2's table holds z^(2^b))
+static void bary_point(const uint64_t* z, unsigned log2n, BaryArgs* a)
+{
+    const Pow2Arg t = host_pow2(z, nullptr);
+    memcpy(a->z, &t.z, 32);
+    memcpy(a->zn, &t.pow2z[log2n], 32);
+}
+int poly_evaluate_lagrange_async(bbg_ctx* ctx, const void* const* d_evals, const int* shifted, size_t count, unsigned log2n, const uint64_t* z,
+                                 void* d_dest, void** d_results, hipStream_t st)
+{
+    if (!d_evals || !z || count == 0 || count > (size_t)BARY_MAX || log2n == 0 || log2n > 28) {
+        set_error("evaluate_lagrange: bad argument (1..32 polynomials, 1 <= log2n <= 28)");
+        return BBG_E_INVALID;
+    }
+    BaryArgs a = {};
+    for (size_t k = 0; k < count; k++) {
+        if (!d_evals[k]) { set_error("evaluate_lagrange: null polynomial"); return BBG_E_INVALID; }
+        a.polys[k] = d_evals[k];
+        if (shifted && shifted[k]) a.shifted |= 1u << k;
+    }
+    a.count = (int)count;
+    a.log2n = log2n;
+    bary_point(z, log2n, &a);
+    a.dest = d_dest;
+    if (d_dest) { // W(w^j) at z = w^j would need a derivative: refused before anything is queued
+        if (memcmp(a.zn, FrP::ONE, 32) == 0) { set_error("bbg_kate_opening_lagrange_device: z lies on the domain (z^n = 1)"); return BBG_E_INVALID; }
+    }
+    void* dc = nullptr;
+    int rc = ntt_domain_consts(ctx, log2n, &dc);
+    if (rc) return rc;
+    a.consts = dc;
+    PolyHeader* hdr;
+    Fr* partials;
+    rc = poly_scratch(ctx, count * bary_grid((size_t)1 << log2n), &hdr, &partials);
+    if (rc) return rc;
+    a.partials = partials;
+    a.results = hdr->results;
+    a.flag = &hdr->bary_flag;
+    rc = bary_evaluate(ctx, a, st);
+    if (rc) return rc;
+    *d_results = hdr->results;
+    return BBG_OK;
+}
+int poly_evaluate_lagrange(bbg_ctx* ctx, const void* const* d_evals, const int* shifted, size_t count, unsigned log2n, const uint64_t* z, uint64_t* out,
+                           hipStream_t st)
+{
+    if (!out) { set_error("bbg_poly_evaluate_lagrange: null argument"); return BBG_E_INVALID; }
+    void* d_res = nullptr;
+    int rc = poly_evaluate_lagrange_async(ctx, d_evals, shifted, count, log2n, z, nullptr, &d_res, st);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out, d_res, count * 32, hipMemcpyDeviceToHost, st));
+    BBG_HIP(hipStreamSynchronize(st));
+    return BBG_OK;
+}
+int poly_kate_opening_lagrange(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t* z, uint64_t* f_out, hipStream_t st)
+{
+    if (!d_evals || !d_dest || !z || !f_out || log2n == 0 || log2n > 28) {
+        set_error("bbg_kate_opening_lagrange_device: bad argument (1 <= log2n <= 28)");
+        return BBG_E_INVALID;
+    }
+    if (ranges_overlap(d_evals, d_dest, ((size_t)1 << log2n) * 32)) { set_error("bbg_kate_opening_lagrange_device: dest overlaps the values"); return BBG_E_INVALID; }
+    void* d_res = nullptr;
+    int rc = poly_evaluate_lagrange_async(ctx, &d_evals, nullptr, 1, log2n, z, d_dest, &d_res, st);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(f_out, d_res, 32, hipMemcpyDeviceToHost, st));
     BBG_HIP(hipStreamSynchronize(st));
     return BBG_OK;
 }

@@ -574,6 +574,32 @@ int bbg_prover_evaluate(bbg_prover* p, size_t count, const int* ids, const int* 
     return BBG_OK;
 }
 
+int bbg_prover_evaluate_lagrange(bbg_prover* p, size_t count, const int* ids, const int* shifted, const uint64_t zeta[4], uint64_t* out)
+{
+    CHECK_P(p);
+    if (!ids || !zeta || !out || count == 0 || count > 32) { set_error("bbg_prover_evaluate_lagrange: bad argument (1..32 evaluations per call)"); return BBG_E_INVALID; }
+    if (!p->key_final) { set_error("bbg_prover_evaluate_lagrange: call bbg_prover_finalize_key first"); return BBG_E_INVALID; }
+    if (p->stage < 1) { set_error("bbg_prover_evaluate_lagrange: round 1 has not run for this proof (the wires are not this proof's yet)"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(p->ctx->mu);
+    hipStream_t st = p->ctx->stream;
+    // the Lagrange-form arrays bbg_prover_read_poly returns: round 1 writes wire_lagrange, finalize sigma_lagrange; every later round only reads them
+    const void* ptrs[32];
+    for (size_t k = 0; k < count; k++) {
+        const int id = ids[k];
+        ptrs[k] = nullptr;
+        if (id >= BBG_QP_W_1 && id < BBG_QP_W_1 + p->width) ptrs[k] = p->wire_lagrange[id - BBG_QP_W_1];
+        else if (id >= BBG_QP_SIGMA_1 && id < BBG_QP_SIGMA_1 + p->width) ptrs[k] = p->sigma_lagrange[id - BBG_QP_SIGMA_1];
+        if (!ptrs[k]) { set_error("bbg_prover_evaluate_lagrange: only the wires and the sigmas of this width are resident in Lagrange form"); return BBG_E_INVALID; }
+    }
+    void* d_res = nullptr;
+    int rc = poly_evaluate_lagrange_async(p->ctx, ptrs, shifted, count, p->log2n, zeta, nullptr, &d_res, st);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(p->h_pin + PIN_EVAL, d_res, count * 32, hipMemcpyDeviceToHost, st));
+    BBG_HIP(hipStreamSynchronize(st));
+    memcpy(out, p->h_pin + PIN_EVAL, count * 32);
+    return BBG_OK;
+}
+
 int bbg_prover_linearise(bbg_prover* p, size_t count, const int* ids, const uint64_t* scalars, const uint64_t zeta[4], uint64_t r_eval[4])
 {
     CHECK_P(p);

@@ -247,6 +247,32 @@ int bbg_poly_evaluate(bbg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint
 int bbg_kate_opening(bbg_ctx* ctx, const uint64_t* src, uint64_t* dest, size_t n, const uint64_t z[4], uint64_t f_out[4]);
 int bbg_divide_by_pseudo_vanishing(bbg_ctx* ctx, uint64_t* evals, unsigned log2_src, unsigned log2_target, size_t num_roots_cut);
 
+/* ---- polynomials in LAGRANGE form: n = 2^log2n values f_i = F(w^i) on the domain, w = fr::get_root_of_unity(log2n) = bbg_fr_root_pow(log2n, 1),
+ *      natural order -- the form bbg_srs_lagrange commits to.  These evaluate and open such a polynomial where it lies, without an iFFT.
+ *      Shared by all: Montgomery Fr, every input any representative in [0, 2r) (r itself is a zero), every output canonical;
+ *      1 <= log2n <= 28, 1 <= count <= 32; a null pointer, or a count or log2n out of range, is BBG_E_INVALID and nothing is written.
+ *      Timed under "fr_batch_invert" / "barycentric" (bbg_profile_get); the partial sums live in the evaluation scratch (`scratch` in
+ *      bbg_memory_report, released by bbg_memory_trim). ---- */
+/* fr::batch_invert (ecc/fields/field_impl.hpp:331-359): out[i] = in[i]^-1, zero stays zero.  d_out may BE d_in; any other overlap of the two
+ * is BBG_E_INVALID.  n = 0 does nothing.  One real inversion per 1024 elements (Montgomery's trick).  Asynchronous on the context stream. */
+int bbg_fr_batch_invert_device(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n);
+/* polynomial_arithmetic::compute_barycentric_evaluation (polynomials/polynomial_arithmetic.cpp:811-847) for `count` polynomials in one pass:
+ * out[k] = F_k(z), or F_k(z * w) where shifted[k] != 0 (shifted may be NULL), from F(z) = (z^n - 1)/n * sum_i f_i / (z w^-i - 1); the shifted
+ * form uses the same weights and reads the values one place further on.  d_evals: host array of `count` device addresses.
+ * Two deliberate differences from the reference: (1) the shifted value is the mathematical F(z * w) -- the reference's Lagrange branch passes
+ * zeta where it means the shifted point (kate_commitment_scheme.cpp:429), its coefficient branch two lines below computes F(z * w), which is
+ * what a verifier needs; (2) z ON the domain, z = w^j, is answered exactly, F(z) = f_j and F(z w) = f_{(j+1) mod n} -- the reference's
+ * batch_invert skips the zero denominator and returns a wrong sum.  Synchronous: one host synchronisation, like bbg_poly_evaluate_device. */
+int bbg_poly_evaluate_lagrange_device(bbg_ctx* ctx, const void* const* d_evals, const int* shifted, size_t count, unsigned log2n,
+                                      const uint64_t z[4], uint64_t* out /* count x 4 limbs */);
+/* Host-buffer form for ONE polynomial (what a shim would bind compute_barycentric_evaluation to): upload, evaluate at z, synchronous. */
+int bbg_poly_evaluate_lagrange(bbg_ctx* ctx, const uint64_t* evals, unsigned log2n, const uint64_t z[4], uint64_t out[4]);
+/* The Kate opening quotient in evaluation form: d_dest[i] = W(w^i) = w^-i (F(z) - f_i) / (z w^-i - 1) for W(X) = (F(X) - F(z)) / (X - z), f_out = F(z);
+ * the inverse NTT of d_dest is what bbg_kate_opening_device gives for F's coefficients (top coefficient zero).  d_dest holds n values and must
+ * not overlap d_evals (BBG_E_INVALID).  For z on the domain (z^n = 1) W(w^j) would need a derivative: BBG_E_INVALID, decided on the host before
+ * anything is queued, d_dest untouched.  Synchronous. */
+int bbg_kate_opening_lagrange_device(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t z[4], uint64_t f_out[4]);
+
 /* ---- device memory helpers for hosts that do not link HIP (bbmalloc/bbfree analogue, c_bind.cpp:11-15) ---- */
 int bbg_dev_alloc(bbg_ctx* ctx, size_t bytes, void** d_ptr);
 int bbg_dev_free(bbg_ctx* ctx, void* d_ptr);
@@ -346,6 +372,11 @@ int bbg_prover_round4(bbg_prover* p, const uint64_t alpha[4], const uint64_t pub
  * out[k] = P_ids[k](zeta), or P(zeta * w_n) where shifted[k] != 0 (shifted may be NULL); ids from bbg_quotient_poly /
  * bbg_prover_poly (coefficient forms; BBG_PP_QUOTIENT evaluates all 4n coefficients).  count <= 32. */
 int bbg_prover_evaluate(bbg_prover* p, size_t count, const int* ids, const int* shifted, const uint64_t zeta[4], uint64_t* out);
+/* The same evaluations from the handle's LAGRANGE-form arrays, where they lie (bbg_poly_evaluate_lagrange_device's contract and formula): ids
+ * BBG_QP_W_1 .. W_width and BBG_QP_SIGMA_1 .. SIGMA_width -- the arrays bbg_prover_read_poly(..., BBG_FORM_LAGRANGE, ...) returns; any other id is
+ * BBG_E_INVALID.  Needs a finalised key and round 1 of the current proof; reads only (no round uses those arrays as scratch), so a proof in
+ * progress is not disturbed and its stage does not change.  count <= 32; returns after one host synchronisation. */
+int bbg_prover_evaluate_lagrange(bbg_prover* p, size_t count, const int* ids, const int* shifted, const uint64_t zeta[4], uint64_t* out);
 /* Round 5b (compute_linear_contribution of every widget, prover.cpp:399-407): r(X) = sum_k scalars[k] * P_ids[k](X) (resident as
  * BBG_PP_LINEAR), r_eval = r(zeta). */
 int bbg_prover_linearise(bbg_prover* p, size_t count, const int* ids, const uint64_t* scalars, const uint64_t zeta[4], uint64_t r_eval[4]);
@@ -448,7 +479,8 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
  * Every value of every option gives bit-identical results; they exist for A/B measurements. */
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
- * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul".  enable(…, 1) clears previous samples. */
+ * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul",
+ * "fr_batch_invert", "barycentric".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
