@@ -88,6 +88,13 @@ def load_library():
         "bbg_g1_batch_mul": (cint, [vp, vp, vp, sz, cint, vp]),
         "bbg_g1_batch_mul_device": (cint, [vp, vp, vp, sz, cint, vp]),
         "bbg_srs_scale_powers": (cint, [vp, vp, vp, ctypes.POINTER(vp)]),
+        "bbg_g1_ntt": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
+        "bbg_g1_ntt_device": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
+        "bbg_open_all_prepare": (cint, [vp, vp, ctypes.c_uint, ctypes.POINTER(vp)]),
+        "bbg_open_all_device": (cint, [vp, vp, vp]),
+        "bbg_open_all": (cint, [vp, vp, vp]),
+        "bbg_open_all_device_bytes": (cint, [vp, ctypes.POINTER(sz)]),
+        "bbg_open_all_free": (None, [vp]),
         "bbg_ntt": (cint, [vp, vp, ctypes.c_uint, cint, sz, vp]),
         "bbg_coset_fft_extend": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp]),
         "bbg_quotient_widget_device": (cint, [vp, cint, vp, ctypes.c_uint, vp, vp, vp]),
@@ -172,6 +179,7 @@ EXPORTED_SYMBOLS = [
     "bbg_g1_batch_mul", "bbg_g1_batch_mul_device", "bbg_srs_scale_powers",
     "bbg_fr_batch_invert_device", "bbg_poly_evaluate_lagrange_device", "bbg_poly_evaluate_lagrange", "bbg_kate_opening_lagrange_device",
     "bbg_prover_evaluate_lagrange",
+    "bbg_g1_ntt", "bbg_g1_ntt_device", "bbg_open_all_prepare", "bbg_open_all_device", "bbg_open_all", "bbg_open_all_device_bytes", "bbg_open_all_free",
 ]
 
 
@@ -226,6 +234,36 @@ class Srs:
     def free(self):
         if self.handle:
             self._owner.lib.bbg_srs_free(self.handle)
+            self.handle = None
+
+
+class OpenAll:
+    """A prepared bbg_open_all handle: all n = 2^log2n opening proofs of a polynomial on its own domain per call."""
+
+    def __init__(self, owner, handle, log2n):
+        self._owner, self.handle, self.log2n = owner, handle, log2n
+
+    def open(self, coeffs):
+        """(n, 8) canonical affine proofs, out[m] = commitment to (f(X) - f(w^m)) / (X - w^m), for (n, 4) Montgomery coefficients (bbg_open_all)."""
+        c = _u64(coeffs, 4)
+        if c.shape[0] != 1 << self.log2n:
+            raise ValueError(f"expected {1 << self.log2n} coefficients, got {c.shape[0]}")
+        out = np.zeros((c.shape[0], 8), dtype=np.uint64)
+        self._owner._ck(self._owner.lib.bbg_open_all(self.handle, c.ctypes.data, out.ctypes.data))
+        return out
+
+    def open_device(self, d_coeffs, d_out):
+        """Device pointers; asynchronous on the context stream (bbg_open_all_device)."""
+        self._owner._ck(self._owner.lib.bbg_open_all_device(self.handle, ctypes.c_void_p(d_coeffs), ctypes.c_void_p(d_out)))
+
+    def device_bytes(self):
+        b = ctypes.c_size_t()
+        self._owner._ck(self._owner.lib.bbg_open_all_device_bytes(self.handle, ctypes.byref(b)))
+        return int(b.value)
+
+    def free(self):
+        if self.handle:
+            self._owner.lib.bbg_open_all_free(self.handle)
             self.handle = None
 
 
@@ -395,6 +433,28 @@ class Bbg:
     def g1_batch_mul_device(self, d_points, d_scalars, n, d_out, one_scalar=False):
         self._ck(self.lib.bbg_g1_batch_mul_device(self.ctx, ctypes.c_void_p(d_points), ctypes.c_void_p(d_scalars), n, int(bool(one_scalar)),
                                                   ctypes.c_void_p(d_out)))
+
+    def g1_ntt(self, points, inverse=False):
+        """The NTT over G1 of (n, 8) affine points, n a power of two >= 2: out[k] = sum_j w^(jk) P_j, or n^-1 sum_j w^(-jk) P_j with
+        inverse; canonical affine, infinite outputs in the affine encoding of infinity (bbg_g1_ntt)."""
+        pt = _u64(points, 8)
+        n = pt.shape[0]
+        log2n = n.bit_length() - 1
+        if n == 0 or (1 << log2n) != n:
+            raise ValueError("G1 NTT size must be a power of two")
+        out = np.zeros((n, 8), dtype=np.uint64)
+        self._ck(self.lib.bbg_g1_ntt(self.ctx, pt.ctypes.data, log2n, int(bool(inverse)), out.ctypes.data))
+        return out
+
+    def g1_ntt_device(self, d_points, log2n, d_out, inverse=False):
+        """Device pointers, d_out may be d_points; asynchronous (bbg_g1_ntt_device)."""
+        self._ck(self.lib.bbg_g1_ntt_device(self.ctx, ctypes.c_void_p(d_points), log2n, int(bool(inverse)), ctypes.c_void_p(d_out)))
+
+    def open_all_prepare(self, srs, log2n):
+        """An OpenAll for polynomials of 2^log2n coefficients over the first 2^log2n - 1 points of srs (bbg_open_all_prepare)."""
+        h = ctypes.c_void_p()
+        self._ck(self.lib.bbg_open_all_prepare(self.ctx, srs.handle, log2n, ctypes.byref(h)))
+        return OpenAll(self, h, log2n)
 
     # ---- NTT
     def ntt(self, coeffs, op=FFT, generator_size=0, constant=None):

@@ -155,6 +155,7 @@ void bbg_destroy(bbg_ctx* ctx)
     if (ctx->poly_scratch) (void)hipFree(ctx->poly_scratch);
     if (ctx->fb_table) (void)hipFree(ctx->fb_table);
     if (ctx->vb_tables) (void)hipFree(ctx->vb_tables);
+    if (ctx->ecntt_work) (void)hipFree(ctx->ecntt_work);
     if (ctx->aux_stream) {
         for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
             (void)hipStreamDestroy(ctx->aux_streams[k]);
@@ -399,7 +400,7 @@ int bbg_memory_report(bbg_ctx* ctx, bbg_memory_info* out)
     for (const auto& kv : ctx->dpv_tables) out->ntt_tables += (size_t)32 << ((kv.first >> 8) & 0xff); // poly_dpv_table: one Fr per target-domain point
     out->msm_arena = ctx->msm.bytes + ctx->msm_tiny.bytes;
     out->scratch = ctx->ntt_scratch_bytes + ctx->staging_bytes + ctx->poly_scratch_bytes + ctx->gp_totals_bytes + ctx->quot_setup_bytes +
-                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES + ctx->fb_table_bytes + ctx->vb_tables_bytes;
+                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES + ctx->fb_table_bytes + ctx->vb_tables_bytes + ctx->ecntt_work_bytes;
     prover_report(ctx, &out->prover_keys, &out->live_provers);
     out->total = out->srs_points + out->srs_tables + out->ntt_tables + out->msm_arena + out->scratch + out->prover_keys;
     BBG_HIP(hipMemGetInfo(&out->device_free, &out->device_total));
@@ -434,6 +435,7 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released)
         drop(&ctx->fb_table, &ctx->fb_table_bytes); // the next fixed-base call rebuilds it
         ctx->fb_table_valid = false;
         drop(&ctx->vb_tables, &ctx->vb_tables_bytes);
+        drop(&ctx->ecntt_work, &ctx->ecntt_work_bytes);
         drop(&ctx->msm.buf, &ctx->msm.bytes);
         drop(&ctx->msm_tiny.buf, &ctx->msm_tiny.bytes);
         ctx->msm_tiny_layout = 0;
@@ -889,7 +891,7 @@ int bbg_srs_lagrange(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, bbg_srs** out)
         e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), ctx->stream);
     }
     if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_lagrange: working set", __FILE__, __LINE__);
-    if (rc == BBG_OK) rc = ecntt_run(ctx, srs->s.points, log2n, d_work, d_plain, d_flag, ctx->stream);
+    if (rc == BBG_OK) rc = ecntt_run(ctx, srs->s.points, log2n, 1, d_work, d_plain, d_flag, ctx->stream);
     if (rc == BBG_OK) {
         e = hipMemcpyAsync(h_flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_lagrange: flag copy", __FILE__, __LINE__);
@@ -908,6 +910,88 @@ int bbg_srs_lagrange(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, bbg_srs** out)
     }
     *out = res;
     return BBG_OK;
+}
+
+// The general transform on plain device arrays: the working set is the context's, the output may be the input, an infinite output is data.
+int bbg_g1_ntt_device(bbg_ctx* ctx, const void* d_points_affine, unsigned log2n, int inverse, void* d_out_affine)
+{
+    CHECK_CTX(ctx);
+    if (!d_points_affine || !d_out_affine) { set_error("bbg_g1_ntt_device: null argument"); return BBG_E_INVALID; }
+    if (log2n < 1 || log2n > 28) { set_error("bbg_g1_ntt_device: log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = ensure_buffer(&ctx->ecntt_work, &ctx->ecntt_work_bytes, ((size_t)1 << log2n) * 128);
+    if (rc) return rc;
+    return ecntt_run(ctx, d_points_affine, log2n, inverse, ctx->ecntt_work, d_out_affine, nullptr, ctx->stream);
+}
+
+int bbg_g1_ntt(bbg_ctx* ctx, const uint64_t* points_affine, unsigned log2n, int inverse, uint64_t* out_affine)
+{
+    CHECK_CTX(ctx);
+    if (!points_affine || !out_affine) { set_error("bbg_g1_ntt: null argument"); return BBG_E_INVALID; }
+    if (log2n < 1 || log2n > 28) { set_error("bbg_g1_ntt: log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t n = (size_t)1 << log2n;
+    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 64);
+    if (rc == BBG_OK) rc = ensure_buffer(&ctx->ecntt_work, &ctx->ecntt_work_bytes, n * 128);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(ctx->staging, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    rc = ecntt_run(ctx, ctx->staging, log2n, inverse, ctx->ecntt_work, ctx->staging, nullptr, ctx->stream); // transformed in place
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out_affine, ctx->staging, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ all openings (open_all.hip)
+int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_open_all** out)
+{
+    CHECK_CTX(ctx);
+    if (!srs || !out) { set_error("bbg_open_all_prepare: null argument"); return BBG_E_INVALID; }
+    if (log2n < 1 || log2n > 27) { set_error("bbg_open_all_prepare: log2n must be 1 .. 27"); return BBG_E_INVALID; }
+    if (((size_t)1 << log2n) > srs->s.n) { set_error("bbg_open_all_prepare: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
+    if (srs->s.device != ctx->device) { set_error("bbg_open_all_prepare: the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return open_all_prepare(ctx, srs->s.points, log2n, out);
+}
+
+int bbg_open_all_device(struct bbg_open_all* h, const void* d_coeffs, void* d_out_affine)
+{
+    if (!h || !d_coeffs || !d_out_affine) { set_error("bbg_open_all_device: null argument"); return BBG_E_INVALID; }
+    CHECK_CTX(h->ctx);
+    std::lock_guard<std::mutex> lk(h->ctx->mu);
+    return open_all_run(h, d_coeffs, d_out_affine, h->ctx->stream);
+}
+
+int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_affine)
+{
+    if (!h || !coeffs || !out_affine) { set_error("bbg_open_all: null argument"); return BBG_E_INVALID; }
+    bbg_ctx* ctx = h->ctx;
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t n = (size_t)1 << h->log2n;
+    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 96);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging; // proofs | coefficients
+    BBG_HIP(hipMemcpyAsync(st + n * 64, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = open_all_run(h, st + n * 64, st, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out_affine, st, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
+int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes)
+{
+    if (!h || !bytes) { set_error("bbg_open_all_device_bytes: null argument"); return BBG_E_INVALID; }
+    *bytes = open_all_bytes(h->log2n);
+    return BBG_OK;
+}
+
+void bbg_open_all_free(struct bbg_open_all* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->ctx->device);
+    open_all_release(h);
 }
 
 int bbg_srs_retain(bbg_srs* srs)

@@ -161,9 +161,22 @@ struct bbg_ctx {
     // the Lagrange transform's stages under "ecntt_mul" = 1
     void* vb_tables = nullptr;
     size_t vb_tables_bytes = 0;
+    // bbg_g1_ntt*: the XYZZ working set of the transform (128 B per point), grown on demand
+    void* ecntt_work = nullptr;
+    size_t ecntt_work_bytes = 0;
     int batch_mul_glv = 1;           // option "batch_mul_glv": 1 = windowed GLV (xyzz_mul_glv), 0 = the bit-serial double-and-add (xyzz_mul_fr), A/B
     long batch_mul_lanes = 1L << 17; // option "batch_mul_lanes": lanes of the variable-base kernels = tables held (a multiple of 64; 2^17 = two waves per SIMD)
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
+};
+
+// bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle
+struct bbg_open_all {
+    bbg_ctx* ctx = nullptr;
+    unsigned log2n = 0;
+    void* s_hat = nullptr;  // 2n x 64 B affine, infinities possible
+    void* work2 = nullptr;  // 2n x 128 B XYZZ: the inverse transform's working array
+    void* work1 = nullptr;  // n x 128 B XYZZ: the forward transform's
+    void* c_hat = nullptr;  // 2n x 32 B Fr
 };
 
 struct bbg_srs {
@@ -270,10 +283,15 @@ int srs_synth_linear(bbg_ctx* ctx, uint64_t a, uint64_t s, size_t n, void* d_poi
 int msm_join(bbg_ctx* ctx, hipStream_t stream);
 int srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, void* d_points, hipStream_t stream);
 int g1_sum_device(bbg_ctx* ctx, const void* d_jacs, size_t n, void* d_out, hipStream_t stream);
-// ecntt.hip: the inverse NTT over G1 behind bbg_srs_lagrange.  d_src: 2^log2n plain affine points (read only); d_work: 2^log2n x 128 B;
-// d_out: 2^log2n x 64 B canonical affine; *d_inf_flag (cleared by the caller on `stream`) is set when an output is the point at infinity.
-// Queues only, no host synchronisation.
-int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
+// ecntt.hip: the NTT over G1 behind bbg_srs_lagrange, bbg_g1_ntt and bbg_open_all.  d_src: 2^log2n plain affine points (read only, aff_inf()
+// allowed); d_work: 2^log2n x 128 B; d_out: 2^log2n x 64 B canonical affine, may be d_src.  inverse != 0: n^-1 sum_j w_n^(-jk) P_j, else
+// sum_j w_n^(jk) P_j.  d_inf_flag != null: *d_inf_flag (cleared by the caller on `stream`) is set when an output is the point at infinity;
+// null: such an output is stored as aff_inf().  Queues only, no host synchronisation.
+int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, int inverse, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
+// its three steps: d_work[i] = d_src[bitrev(i)] as XYZZ; the log2n stages in place on d_work (bit-reversed in, natural out); d_work -> affine
+int ecntt_load(const void* d_src, unsigned log2n, void* d_work, hipStream_t stream);
+int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t stream);
+int ecntt_normalize(bbg_ctx* ctx, const void* d_work, size_t n, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
 // fixed_base.hip: d_out[i] = d_scalars[i] * B (64 B canonical affine, aff_inf() for an infinite result) from the context's table of B's
 // multiples, which is built on first use and rebuilt for another base.  base_affine: HOST, NULL = the generator; BBG_E_INVALID when it is
 // not on the curve.  Queues only.
@@ -286,4 +304,9 @@ int var_base_mul(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size
 // the lanes (a multiple of 64, at most "batch_mul_lanes") a variable-base kernel with `work` items runs on, and their tables in the
 // context's buffer (1 KiB per lane, grown on demand)
 int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables);
+// open_all.hip
+int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out);
+int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t stream);
+size_t open_all_bytes(unsigned log2n);
+void open_all_release(struct bbg_open_all* h);
 } // namespace bbg

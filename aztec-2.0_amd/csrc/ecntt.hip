@@ -22,17 +22,19 @@
 //   * k_ecntt_normalize  batched conversion to canonical affine (aff_batch_*, curve.hip.h), one inversion per NORM_CH points;
 //                      a point at infinity among the outputs raises a flag (an SRS handle never holds one) and the call fails.
 // All group-law cases (equal / opposite operands, infinities inside the transform) are handled by xyzz_add / xyzz_dbl.
+//
+// The same three steps, each callable on its own (ecntt_load / ecntt_stages / ecntt_normalize), also make the general transform behind
+// bbg_g1_ntt and the two transforms inside bbg_open_all (open_all.hip), which runs the stages on XYZZ working arrays it already holds:
+//   * the stage kernels take the direction as a template parameter.  <true> is the inverse described above; <false> is the forward
+//     transform out[k] = sum_j w_n^(jk) P_j: twiddles from the table of root^(2^b), and no n^-1 in the last stage;
+//   * k_ecntt_normalize<true> stores a point at infinity as aff_inf() and raises no flag.
 #include "bbg_internal.h"
 #include "curve.hip.h"
+#include "ecntt.hip.h" // bit_reverse
 #include "ntt_consts.hip.h"
 #include "var_base.hip.h" // xyzz_mul_fr, xyzz_mul_glv, xyzz_neg
 
 namespace bbg {
-
-__device__ __forceinline__ size_t bit_reverse(size_t i, unsigned bits)
-{
-    return (size_t)(__brevll((unsigned long long)i) >> (64 - bits));
-}
 
 // work[i] = M[bitrev(i)] in XYZZ form (the input permutation of the decimation-in-time schedule)
 __global__ void __launch_bounds__(256) k_ecntt_load(const Affine* __restrict__ src, Xyzz* __restrict__ work, unsigned log2n)
@@ -49,8 +51,11 @@ __global__ void __launch_bounds__(256) k_ecntt_load(const Affine* __restrict__ s
 #ifndef BBG_ECNTT_OCC
 #define BBG_ECNTT_OCC 2
 #endif
+// INV: the inverse transform (twiddles w_n^-1, n^-1 folded into the last stage); the forward one ignores `last`.
+template <bool INV>
 __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last)
 {
+    if (!INV) last = 0;
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ((size_t)1 << (log2n - 1))) return;
     const size_t m = (size_t)1 << s;
@@ -58,7 +63,7 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restr
     const size_t i = ((t >> s) << (s + 1)) + j;
     Xyzz b = xyzz_load(work + i + m);
     if (last || j != 0) {
-        Fr w = pow_from_table(dc->pow2_root_inv, (uint64_t)j << (log2n - 1 - s)); // w_2m^-j = w_n^(-j n / 2m)
+        Fr w = pow_from_table(INV ? dc->pow2_root_inv : dc->pow2_root, (uint64_t)j << (log2n - 1 - s)); // w_2m^-j = w_n^(-j n / 2m); forward: w_2m^j
         if (last) w = fe_mul(w, dc->n_inv);
         b = xyzz_mul_fr(b, fe_reduce_once(fe_from_mont(w)));
     }
@@ -71,9 +76,11 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restr
 // The same stage on the windowed GLV multiplication of var_base.hip.h (option "ecntt_mul" = 1, the default): a fixed number of lanes, each with its
 // 1 KiB table of odd multiples in `tables`, lane t taking the butterflies t, t + lanes, ..  Bit-identical to k_ecntt_stage after the
 // normalisation (the same group elements in another XYZZ representation).
+template <bool INV>
 __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last,
                                                                        Xyzz* __restrict__ tables)
 {
+    if (!INV) last = 0;
     const size_t lanes = (size_t)gridDim.x * blockDim.x;
     const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     Xyzz* table = tables + (size_t)blockIdx.x * 64 * GLV_TABLE; // the wave's 64 tables (blocks of one wave): wave-uniform
@@ -84,7 +91,7 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __r
         const size_t i = ((t >> s) << (s + 1)) + j;
         Xyzz b = xyzz_load(work + i + m);
         if (last || j != 0) {
-            Fr w = pow_from_table(dc->pow2_root_inv, (uint64_t)j << (log2n - 1 - s)); // w_2m^-j = w_n^(-j n / 2m)
+            Fr w = pow_from_table(INV ? dc->pow2_root_inv : dc->pow2_root, (uint64_t)j << (log2n - 1 - s)); // w_2m^-j = w_n^(-j n / 2m); forward: w_2m^j
             if (last) w = fe_mul(w, dc->n_inv);
             b = xyzz_mul_glv(b, fe_reduce_once(fe_from_mont(w)), table);
         }
@@ -97,8 +104,9 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __r
 
 // XYZZ -> canonical affine, NORM_CH consecutive points per thread behind one inversion (the batched conversion of curve.hip.h).  A
 // point at infinity is reported through *inf_flag and stored as the generator, so that whatever is queued behind this kernel still
-// reads valid points; the host discards the result.
+// reads valid points; the host discards the result.  INF_OK: a point at infinity is an ordinary output, stored as aff_inf(); no flag.
 constexpr int NORM_CH = 8;
+template <bool INF_OK>
 __global__ void __launch_bounds__(128) k_ecntt_normalize(const Xyzz* __restrict__ work, Affine* __restrict__ out, size_t n, unsigned* inf_flag)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -117,18 +125,27 @@ __global__ void __launch_bounds__(128) k_ecntt_normalize(const Xyzz* __restrict_
     Fq inv = aff_batch_invert(run);
     for (int e = cnt - 1; e >= 0; e--) {
         const Fq zz = fe_load<FqP>(&work[i0 + e].zz), zzz = fe_load<FqP>(&work[i0 + e].zzz);
-        aff_batch_finish(out + i0 + e, !zz.is_zero_raw(), fe_mul(zz, zzz), prefix[e], inv, aff_generator());
+        aff_batch_finish(out + i0 + e, !zz.is_zero_raw(), fe_mul(zz, zzz), prefix[e], inv, INF_OK ? aff_inf() : aff_generator());
     }
-    if (any_inf) atomicOr(inf_flag, 1u);
+    if (!INF_OK && any_inf) atomicOr(inf_flag, 1u);
 }
 
-// Queues the whole transform on `st`: d_src = 2^log2n plain affine points (read only), d_work = 2^log2n x 128 B, d_out = 2^log2n x 64 B,
-// d_inf_flag = one word the caller has cleared on `st`.  No host synchronisation.
-int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t st)
+// work[i] = src[bitrev(i)] in XYZZ form on `st`: d_src = 2^log2n plain affine points (read only, aff_inf() allowed), d_work = 2^log2n x 128 B.
+int ecntt_load(const void* d_src, unsigned log2n, void* d_work, hipStream_t st)
+{
+    const size_t n = (size_t)1 << log2n;
+    hipLaunchKernelGGL(k_ecntt_load, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Affine*)d_src, (Xyzz*)d_work, log2n);
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+// The log2n stages on `st`, in place on d_work (2^log2n XYZZ points in bit-reversed order; natural order afterwards).  inverse != 0: with
+// w_n^-1 and n^-1, else with w_n and no scaling.  The lanes' tables come from the context (var_base_tables) under "ecntt_mul" = 1.
+int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t st)
 {
     if (log2n < 1 || log2n > 28) { set_error("ecntt: log2n out of range (1 .. 28)"); return BBG_E_INVALID; }
     void* consts = nullptr;
-    int rc = ntt_domain_consts(ctx, log2n, &consts); // root_inv^(2^b) and n^-1 of the scalar NTT's domain
+    int rc = ntt_domain_consts(ctx, log2n, &consts); // root^(2^b), root_inv^(2^b) and n^-1 of the scalar NTT's domain
     if (rc) return rc;
     const size_t n = (size_t)1 << log2n;
     size_t lanes = 0;
@@ -137,25 +154,45 @@ int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, void* d_work, voi
         rc = var_base_tables(ctx, n / 2, &lanes, &tables);
         if (rc) return rc;
     }
-    {
-        ProfScope ps(ctx, "ecntt_stages", st);
-        hipLaunchKernelGGL(k_ecntt_load, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Affine*)d_src, (Xyzz*)d_work, log2n);
-        for (unsigned s = 0; s < log2n; s++) {
-            const int last = s + 1 == log2n ? 1 : 0;
-            if (ctx->ecntt_mul)
-                hipLaunchKernelGGL(k_ecntt_stage_glv, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last,
-                                   (Xyzz*)tables);
-            else
-                hipLaunchKernelGGL(k_ecntt_stage, dim3(grid_for(n / 2, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last);
-        }
-    }
-    {
-        ProfScope ps(ctx, "ecntt_normalize", st);
-        hipLaunchKernelGGL(k_ecntt_normalize, dim3(grid_for((n + NORM_CH - 1) / NORM_CH, 128)), dim3(128), 0, st, (const Xyzz*)d_work, (Affine*)d_out, n,
-                           d_inf_flag);
+    auto glv = inverse ? k_ecntt_stage_glv<true> : k_ecntt_stage_glv<false>;
+    auto serial = inverse ? k_ecntt_stage<true> : k_ecntt_stage<false>;
+    for (unsigned s = 0; s < log2n; s++) {
+        const int last = s + 1 == log2n ? 1 : 0;
+        if (ctx->ecntt_mul)
+            hipLaunchKernelGGL(glv, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last, (Xyzz*)tables);
+        else
+            hipLaunchKernelGGL(serial, dim3(grid_for(n / 2, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last);
     }
     BBG_HIP(hipGetLastError());
     return BBG_OK;
+}
+
+// d_out[i] = d_work[i] as canonical affine on `st`, n points.  d_inf_flag != null: a point at infinity sets *d_inf_flag (cleared by the
+// caller on `st`) and is stored as the generator; null: it is stored as aff_inf().
+int ecntt_normalize(bbg_ctx* ctx, const void* d_work, size_t n, void* d_out, unsigned* d_inf_flag, hipStream_t st)
+{
+    ProfScope ps(ctx, "ecntt_normalize", st);
+    const dim3 grid(grid_for((n + NORM_CH - 1) / NORM_CH, 128));
+    if (d_inf_flag)
+        hipLaunchKernelGGL(k_ecntt_normalize<false>, grid, dim3(128), 0, st, (const Xyzz*)d_work, (Affine*)d_out, n, d_inf_flag);
+    else
+        hipLaunchKernelGGL(k_ecntt_normalize<true>, grid, dim3(128), 0, st, (const Xyzz*)d_work, (Affine*)d_out, n, (unsigned*)nullptr);
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+// Queues the whole transform on `st`: d_src = 2^log2n plain affine points (read only), d_work = 2^log2n x 128 B, d_out = 2^log2n x 64 B
+// (may be d_src), d_inf_flag = one word the caller has cleared on `st`, or null (ecntt_normalize).  No host synchronisation.
+int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, int inverse, void* d_work, void* d_out, unsigned* d_inf_flag, hipStream_t st)
+{
+    if (log2n < 1 || log2n > 28) { set_error("ecntt: log2n out of range (1 .. 28)"); return BBG_E_INVALID; }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        int rc = ecntt_load(d_src, log2n, d_work, st);
+        if (rc == BBG_OK) rc = ecntt_stages(ctx, d_work, log2n, inverse, st);
+        if (rc) return rc;
+    }
+    return ecntt_normalize(ctx, d_work, (size_t)1 << log2n, d_out, d_inf_flag, st);
 }
 
 } // namespace bbg

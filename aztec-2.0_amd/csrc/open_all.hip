@@ -1,0 +1,174 @@
+// All n opening proofs of one polynomial on its own domain for gfx950 (bbg_open_all): the Feist-Khovratovich construction.
+//
+// For f = sum_i f_i X^i of degree below n = 2^log2n, the points s_0 .. s_(n-2) of a string and w = w_n, the proof at w^m is the commitment
+// to (f(X) - f(w^m)) / (X - w^m).  Its coefficients are q_j = sum_(i > j) f_i w^(m (i-1-j)), so
+//
+//     proof_m = sum_j q_j s_j = sum_k w^(m k) h_k,      h_k = sum_(i = k+1)^(n-1) f_i s_(i-1-k)   (k <= n-2),   h_(n-1) = infinity:
+//
+// the proofs are the forward G1 NTT of h, and h is a Toeplitz matrix of the f_i applied to the s_j -- the first n entries of a cyclic
+// convolution of length 2n:
+//
+//     s^ = (s_(n-2), s_(n-3), .., s_0, then n+1 infinities)
+//     c^ = (f_(n-1), then n+1 zeros, then f_1, .., f_(n-2))
+//     h  = the first n entries of iNTT_G1,2n( NTT_Fr,2n(c^) o NTT_G1,2n(s^) )
+//
+// (entry k of the convolution is sum_i c^_(k-i) s^_i over i <= n-2: c^_0 pairs s^_k = s_(n-2-k) with f_(n-1), and c^_(2n-d), d = i - k in
+// 1 .. n-2, pairs s_(n-2-i) with f_(n-d) -- f_a s_(a-1-k) for every a in k+1 .. n-1; for k = n-1 every index k - i lands on a zero of c^).
+// f_0 is never read.  tests/tools/open_all_model.py is this on the oracle's group operations, checked against the quotient definition.
+//
+// bbg_open_all_prepare computes NTT_G1,2n(s^) once (k_open_all_srs + the forward transform of ecntt.hip) and keeps it as 2n affine points,
+// infinities among them where they occur.  A call then queues, on one stream and without a host synchronisation:
+//   * k_open_all_coeffs     builds c^ from the coefficients;
+//   * the Fr NTT at 2n      (ntt.hip);
+//   * k_open_all_pointwise  work[bitrev(i)] = c^_hat[i] * s^_hat[i] by xyzz_mul_glv, written as XYZZ straight into the inverse transform's
+//                           working array in the order its first stage wants: no affine normalisation and no load pass in between.  The
+//                           shape of the GLV stage kernel: a fixed number of 64-thread blocks, two waves per SIMD, lane t taking the items
+//                           t, t + lanes, .., each lane with its 1 KiB table of odd multiples from var_base_tables;
+//   * the inverse stages at 2n (ecntt_stages);
+//   * k_open_all_fold       the first n entries, bit-reversed, into the size-n working array, still XYZZ;
+//   * the forward stages at n;
+//   * one normalisation, which writes a proof at infinity as aff_inf() (f constant, for one).
+#include "bbg_internal.h"
+#include "curve.hip.h"
+#include "ecntt.hip.h" // bit_reverse
+#include "var_base.hip.h"
+
+namespace bbg {
+
+// s^[i] = s_(n-2-i) for i <= n-2, aff_inf() above, 2n entries
+__global__ void __launch_bounds__(256) k_open_all_srs(const Affine* __restrict__ srs, Affine* __restrict__ s_hat, unsigned log2n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = (size_t)1 << log2n;
+    if (i >= 2 * n) return;
+    aff_store(s_hat + i, i + 2 <= n ? aff_load(srs + (n - 2 - i)) : aff_inf());
+}
+
+// c^[0] = f_(n-1), c^[n+1+i] = f_i for i = 1 .. n-2, zero elsewhere, 2n entries.  The words are copied as they come (any representative).
+__global__ void __launch_bounds__(256) k_open_all_coeffs(const Fr* __restrict__ f, Fr* __restrict__ c_hat, unsigned log2n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = (size_t)1 << log2n;
+    if (i >= 2 * n) return;
+    Fr v = Fr::zero();
+    if (i == 0) v = fe_load<FrP>(f + (n - 1));
+    else if (i >= n + 2) v = fe_load<FrP>(f + (i - n - 1));
+    fe_store<FrP>(c_hat + i, v);
+}
+
+// work[bitrev(i)] = c_hat[i] * s_hat[i], i < 2^log2m.  Two waves per SIMD, no LDS, no scratch (the register budget of k_ecntt_stage_glv,
+// whose loop body this is without the butterfly).
+__global__ void __launch_bounds__(64, 2) k_open_all_pointwise(const Affine* __restrict__ s_hat, const Fr* __restrict__ c_hat, Xyzz* __restrict__ work, unsigned log2m,
+                                                              Xyzz* __restrict__ tables)
+{
+    const size_t lanes = (size_t)gridDim.x * blockDim.x;
+    const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Xyzz* table = tables + (size_t)blockIdx.x * 64 * GLV_TABLE; // the wave's 64 tables (blocks of one wave): wave-uniform
+#pragma unroll 1
+    for (size_t i = lane; i < ((size_t)1 << log2m); i += lanes) {
+        const Affine a = aff_load(s_hat + i);
+        const Xyzz p = aff_is_inf(a) ? xyzz_inf() : xyzz_from_affine(a);
+        const Fr k = fe_reduce_once(fe_from_mont(fe_load<FrP>(c_hat + i)));
+        xyzz_store(work + bit_reverse(i, log2m), xyzz_mul_glv(p, k, table));
+    }
+}
+
+// dst[i] = src[bitrev(i)], i < 2^log2n: the first half of the 2n results as the input of the size-n transform
+__global__ void __launch_bounds__(256) k_open_all_fold(const Xyzz* __restrict__ src, Xyzz* __restrict__ dst, unsigned log2n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ((size_t)1 << log2n)) return;
+    xyzz_store(dst + i, xyzz_load(src + bit_reverse(i, log2n)));
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+size_t open_all_bytes(unsigned log2n)
+{
+    const size_t n = (size_t)1 << log2n;
+    return 2 * n * 64 + 2 * n * 128 + n * 128 + 2 * n * 32;
+}
+
+void open_all_release(struct bbg_open_all* h)
+{
+    if (h->s_hat) (void)hipFree(h->s_hat);
+    if (h->work2) (void)hipFree(h->work2);
+    if (h->work1) (void)hipFree(h->work1);
+    if (h->c_hat) (void)hipFree(h->c_hat);
+    delete h;
+}
+
+// d_srs_points: at least 2^log2n - 1 plain affine points on the context's device, read once.  Synchronises the stream before it returns,
+// so the caller may free the points at once.
+int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out)
+{
+    const size_t n = (size_t)1 << log2n;
+    hipStream_t st = ctx->stream;
+    struct bbg_open_all* h = new struct bbg_open_all;
+    h->ctx = ctx;
+    h->log2n = log2n;
+    int rc = BBG_OK;
+    hipError_t e = hipMalloc(&h->s_hat, 2 * n * 64);
+    if (e == hipSuccess) e = hipMalloc(&h->work2, 2 * n * 128);
+    if (e == hipSuccess) e = hipMalloc(&h->work1, n * 128);
+    if (e == hipSuccess) e = hipMalloc(&h->c_hat, 2 * n * 32);
+    if (e != hipSuccess) rc = hip_fail(e, "bbg_open_all_prepare: the handle's buffers", __FILE__, __LINE__);
+    if (rc == BBG_OK) {
+        ProfScope ps(ctx, "open_all_prepare", st);
+        hipLaunchKernelGGL(k_open_all_srs, dim3(grid_for(2 * n, 256)), dim3(256), 0, st, (const Affine*)d_srs_points, (Affine*)h->s_hat, log2n);
+        rc = ecntt_run(ctx, h->s_hat, log2n + 1, 0, h->work2, h->s_hat, nullptr, st); // in place; infinite outputs are kept as such
+    }
+    if (rc == BBG_OK) {
+        e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = hip_fail(e, "bbg_open_all_prepare", __FILE__, __LINE__);
+    }
+    if (rc) {
+        open_all_release(h);
+        return rc;
+    }
+    *out = h;
+    return BBG_OK;
+}
+
+// d_coeffs: 2^log2n Montgomery Fr (read only); d_out: 2^log2n x 64 B.  Queues only.
+int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t st)
+{
+    bbg_ctx* ctx = h->ctx;
+    const unsigned log2n = h->log2n, log2m = log2n + 1;
+    const size_t n = (size_t)1 << log2n, m = 2 * n;
+    // the largest table set of the call first (the stages ask for at most m / 2 lanes): the buffer does not move between the launches
+    size_t lanes = 0;
+    void* tables = nullptr;
+    int rc = var_base_tables(ctx, m, &lanes, &tables);
+    if (rc) return rc;
+    {
+        ProfScope ps(ctx, "open_all_coeffs", st);
+        hipLaunchKernelGGL(k_open_all_coeffs, dim3(grid_for(m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, (Fr*)h->c_hat, log2n);
+    }
+    rc = ntt_run(ctx, h->c_hat, log2m, BBG_FFT, 0, nullptr, st);
+    if (rc) return rc;
+    {
+        ProfScope ps(ctx, "open_all_pointwise", st);
+        hipLaunchKernelGGL(k_open_all_pointwise, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (const Affine*)h->s_hat, (const Fr*)h->c_hat, (Xyzz*)h->work2, log2m,
+                           (Xyzz*)tables);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        rc = ecntt_stages(ctx, h->work2, log2m, 1, st);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(ctx, "open_all_fold", st);
+        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Xyzz*)h->work2, (Xyzz*)h->work1, log2n);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        rc = ecntt_stages(ctx, h->work1, log2n, 0, st);
+        if (rc) return rc;
+    }
+    rc = ecntt_normalize(ctx, h->work1, n, d_out, nullptr, st);
+    if (rc) return rc;
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+} // namespace bbg

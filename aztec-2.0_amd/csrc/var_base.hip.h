@@ -1,5 +1,5 @@
 // Variable-base scalar multiplication k * P over BN254 G1 for gfx950: the bit-serial double-and-add (xyzz_mul_fr) and the windowed GLV
-// form (xyzz_mul_glv) that var_base.hip and ecntt.hip share.
+// form (xyzz_mul_glv) that var_base.hip, ecntt.hip and open_all.hip share.
 //
 // xyzz_mul_glv has the shape of the reference's element::mul_with_endomorphism (ecc/groups/element_impl.hpp:593-663): the scalar is split
 // against the cube root of unity lambda, lambda (x, y) = (beta x, y), into two halves below 2^128 which walk one table of odd multiples

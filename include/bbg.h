@@ -174,6 +174,47 @@ int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t
  * in place); an output that overlaps the points in any other way, or overlaps the scalars, is refused with BBG_E_INVALID. */
 int bbg_g1_batch_mul_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int one_scalar, void* d_out_affine);
 
+/* The NTT over G1 on plain arrays of points (no counterpart in the reference beyond the recursion inside transform_srs): with n = 2^log2n,
+ * 1 <= log2n <= 28, and w_n = fr::get_root_of_unity(log2n), natural order in and out,
+ *     out[k] = sum_j w_n^(j k) P_j            (inverse == 0)
+ *     out[k] = n^-1 sum_j w_n^(-j k) P_j      (inverse != 0; what bbg_srs_lagrange computes, bit for bit).
+ * points: 64-byte Montgomery affine, any representative in [0, 2p) per coordinate; the affine encoding of infinity is accepted.  Points are
+ * not checked to be on the curve.  out: canonical Montgomery affine, and an output at infinity is DATA here, written exactly as
+ * bbg_g1_fixed_base_mul writes it (bit 63 of x.data[3] set, every other bit zero) -- bbg_srs_lagrange, whose result must be an SRS, keeps
+ * failing with BBG_E_INFINITY.  The working set, 128 bytes per point, is the context's (counted under `scratch` in bbg_memory_report,
+ * released by bbg_memory_trim), as are the lanes' tables of bbg_g1_batch_mul under "ecntt_mul" = 1.  Null pointers and log2n outside
+ * 1 .. 28 are BBG_E_INVALID.  Timed under "ecntt_stages" / "ecntt_normalize" (bbg_profile_get). */
+int bbg_g1_ntt(bbg_ctx* ctx, const uint64_t* points_affine, unsigned log2n, int inverse, uint64_t* out_affine);
+/* Device-resident: device pointers, asynchronous on the context stream, no host synchronisation once the working set has its size.
+ * d_out_affine may BE d_points_affine. */
+int bbg_g1_ntt_device(bbg_ctx* ctx, const void* d_points_affine, unsigned log2n, int inverse, void* d_out_affine);
+
+/* ---- All openings at once: the KZG proofs of one polynomial at every point of its domain (Feist-Khovratovich, csrc/open_all.hip; no
+ *      counterpart in the reference, whose compute_kate_opening_coefficients + pippenger gives one).  With n = 2^log2n, s_j the first n - 1
+ *      points of an SRS and f = sum_(i<n) f_i X^i:
+ *          out[m] = commitment over the s_j to (f(X) - f(w_n^m)) / (X - w_n^m),   m = 0 .. n-1
+ *                 = sum_k w_n^(m k) h_k,   h_k = sum_(i=k+1)^(n-1) f_i s_(i-1-k)  (k <= n-2),  h_(n-1) = infinity.
+ *      h is a Toeplitz product, taken as a cyclic convolution of length 2n: one Fr NTT, 2n point-scalar products, one inverse G1 NTT at
+ *      2n, one forward G1 NTT at n -- instead of n calls of bbg_kate_opening_device + bbg_msm. ---- */
+struct bbg_open_all; /* the handle; no typedef, because bbg_open_all is also the name of the host entry point below */
+/* Prepares openings of polynomials of n = 2^log2n coefficients, 1 <= log2n <= 27, n <= bbg_srs_num_points(srs): reads the first n - 1
+ * points of `srs` once, transforms them (a forward G1 NTT at 2n) and synchronises.  The handle keeps the context and NOTHING of the SRS:
+ * freeing `srs` afterwards is legal.  It owns its device memory -- 2n x 64 B of transformed points, 2n x 128 B + n x 128 B of XYZZ
+ * working arrays, 2n x 32 B of scalars: 576 n bytes, bbg_open_all_device_bytes -- which bbg_memory_report does not count and
+ * bbg_memory_trim does not touch.  Null pointers, log2n outside 1 .. 27 and n above the SRS length are BBG_E_INVALID.  The SRS is NOT
+ * required to be a powers string: the definition above holds for any points. */
+int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_open_all** out);
+/* d_coeffs: n Montgomery Fr coefficients on the device (any representative in [0, 2r)), read only; f_0 is never read.  d_out_affine:
+ * n x 64 B canonical Montgomery affine; a proof at infinity (every one of a constant f) is written as bbg_g1_ntt writes it.  Asynchronous
+ * on the context stream, no host synchronisation; calls through one handle are ordered by that stream and share its working arrays.
+ * Timed under "open_all_coeffs", "ntt_pass", "open_all_pointwise", "ecntt_stages", "open_all_fold", "ecntt_normalize". */
+int bbg_open_all_device(struct bbg_open_all* h, const void* d_coeffs, void* d_out_affine);
+/* Host arrays; returns when the proofs are in out_affine. */
+int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_affine);
+int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes);
+/* Releases the handle and its device memory (a device synchronisation); must precede bbg_destroy of its context. */
+void bbg_open_all_free(struct bbg_open_all* h);
+
 /* ---- NTT family: replaces polynomial_arithmetic::fft/ifft/coset_fft/coset_ifft/... on fr* coeffs
  *      (polynomials/polynomial_arithmetic.cpp:374-484) and the C bindings coset_fft_with_generator_shift / ifft
  *      (plonk/proof_system/prover/c_bind.cpp:59-76). ----------------------------------------------------------- */
@@ -433,7 +474,8 @@ typedef struct bbg_memory_info {
     size_t srs_tables;     /* window tables of every live SRS of this context, all widths */
     size_t ntt_tables;     /* per-domain twiddle / coset tables (5 x 32n bytes per prepared size) */
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
-    size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table */
+    size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
+                              variable-base lanes' tables, the working set of bbg_g1_ntt */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
@@ -475,12 +517,13 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
  * launch set; 0 / 1 = one launch set each),
  * "batch_mul_glv" (1 = bbg_g1_batch_mul* multiplies with the windowed GLV form, default; 0 = with the bit-serial double-and-add, A/B),
  * "batch_mul_lanes" (a multiple of 64 in 64 .. 2^20, default 2^17: lanes of the variable-base kernels, each holding a 1 KiB table and walking
- * the points with that stride), "ecntt_mul" (1 = bbg_srs_lagrange's stages multiply with the windowed GLV form, default; 0 = bit-serially, A/B).
+ * the points with that stride), "ecntt_mul" (1 = the stages of the G1 transforms -- bbg_srs_lagrange, bbg_g1_ntt, bbg_open_all -- multiply with the
+ * windowed GLV form, default; 0 = bit-serially, A/B).
  * Every value of every option gives bit-identical results; they exist for A/B measurements. */
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
  * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul",
- * "fr_batch_invert", "barycentric".  enable(…, 1) clears previous samples. */
+ * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
