@@ -6,7 +6,14 @@ Every comparison is bit-exact on canonical Montgomery affine words.  Expected va
 tests/test_gpu_lagrange_srs.py) or from identities of the transform.  Oracle transforms are computed once per module and left unchanged.
 
 The three settings every case at 2^6 runs under: the defaults, "ecntt_mul" = 0 (bit-serial stages) and "batch_mul_lanes" = 64, with which
-the GLV stage kernel's lane-stride loop goes round more than once from 2^8 on -- so those cases include 2^8."""
+the GLV stage kernel's lane-stride loop goes round more than once from 2^8 on -- so those cases include 2^8.
+
+Designed inputs (section 6, tests/tools/g1_design.py): points [a_j] G whose scalars solve a linear system mod r, so that EVERY stage of the
+transform, in both directions, has a butterfly with A = t (the doubling branch of xyzz_add) and one with A = -t (result at infinity) --
+from stage 1 on under a twiddle other than 1 and between non-normalised XYZZ operands, in the inverse's last stage behind n^-1, at 2^8
+under 64 lanes beyond the first round of the lane-stride loop.  Hashed inputs never give a stage kernel either.  The want is [y_k] G for
+the integers y_k of the design's model, made by bbg_g1_fixed_base_mul and held to the oracle; tests/test_g1_design_cpu.py asserts that
+the designs meet the coincidences they claim."""
 import contextlib
 import ctypes
 
@@ -14,6 +21,7 @@ import numpy as np
 import pytest
 
 import coarse_inputs as ci
+import g1_design as gd
 import lagrange_model as lm
 import open_all_model as oa
 
@@ -215,3 +223,63 @@ def test_errors(bbg, pkg, cases):
     assert bbg.memory_report()["scratch"] >= n * 128
     assert bbg.memory_trim() >= n * 128
     assert np.array_equal(bbg.g1_ntt(big), first)
+
+
+# 6 ------------------------------------------------------------------------------------------------ designed discrete logarithms
+def mont(vals):
+    return ci.to_words([ci.to_mont(v % ci.R_MOD, 0) for v in vals])
+
+
+@pytest.fixture(scope="module")
+def designed(bbg, oracle):
+    """(lg, inverse) -> (points [a_j] G, want [y_k] G) of g1_design.design_ntt, both by bbg_g1_fixed_base_mul (another kernel, with an oracle
+    parity test of its own), made on first use.  The want is held to the oracle: in full by the model's transform of the points up to
+    2^6; at 2^8 by oracle.g1_mul at sixteen indices, the infinite outputs and their butterfly partners among them."""
+    made = {}
+
+    def get(lg, inverse):
+        if (lg, inverse) not in made:
+            n = 1 << lg
+            a, y, report = gd.design_ntt(lg, inverse, SEED + 600 + lg)
+            assert sorted(report) == list(range(lg)) and all(eq >= 1 and op >= 1 for eq, op, _ in report.values()), report
+            pts, want = bbg.g1_fixed_base_mul(mont(a)), bbg.g1_fixed_base_mul(mont(y))
+            infinite = [k for k in range(n) if y[k] == 0]
+            assert len(infinite) == 2  # the last stage's A = t and A = -t
+            for k in range(n):
+                assert np.array_equal(want[k], oa.aff_infinity()) == (k in infinite), f"[y_{k}] G: infinity in the wrong place"
+            if lg <= 6:
+                check(want, oa.g1_ntt(oracle, pts, inverse=inverse), f"2^{lg}, inverse = {inverse}: [y_k] G against the oracle's transform")
+            else:
+                ks = infinite + [k ^ (n // 2) for k in infinite]
+                rng = np.random.default_rng(SEED + 601)
+                while len(ks) < 16:
+                    k = int(rng.integers(0, n))
+                    if k not in ks:
+                        ks.append(k)
+                G = oracle.g1_generator()
+                by_oracle = oa.canon_points(oracle, np.stack([oracle.g1_mul(G, s) for s in mont([y[k] for k in ks])]))
+                check(want[ks], by_oracle, f"2^{lg}, inverse = {inverse}: [y_k] G against oracle.g1_mul at {ks}")
+            made[(lg, inverse)] = (pts, want)
+        return made[(lg, inverse)]
+    return get
+
+
+@pytest.mark.parametrize("inverse", [False, True], ids=["forward", "inverse"])
+@pytest.mark.parametrize("setting,lgs", [("default", (3, 6)), ("ecntt_mul0", (3, 6)), ("lanes64", (3, 6, 8))], ids=["default", "ecntt_mul0", "lanes64"])
+def test_designed_coincidences_in_every_stage(bbg, designed, setting, lgs, inverse):
+    with settings(bbg, setting):
+        for lg in lgs:
+            pts, want = designed(lg, inverse)
+            what = f"designed 2^{lg}, {setting}, inverse = {inverse}"
+            check(bbg.g1_ntt(pts, inverse=inverse), want, f"{what}, host entry")
+            check(device_ntt(bbg, pts, inverse=inverse), want, f"{what}, device entry")  # and the input unchanged
+            check(device_ntt(bbg, pts, inverse=inverse, in_place=True), want, f"{what}, device entry in place")
+            # back again, the two infinite outputs among the inputs as data
+            check(bbg.g1_ntt(want, inverse=not inverse), pts, f"{what}, round trip")
+
+
+@pytest.mark.parametrize("inverse", [False, True], ids=["forward", "inverse"])
+def test_designed_coincidences_with_lifted_coordinates(bbg, designed, inverse):
+    pts, want = designed(6, inverse)
+    check(bbg.g1_ntt(lift(pts), inverse=inverse), want, f"designed 2^6, inverse = {inverse}, coordinates in [p, 2p)")
+    check(bbg.g1_ntt(lift(want), inverse=not inverse), pts, f"designed 2^6, inverse = {inverse}, round trip from coordinates in [p, 2p)")

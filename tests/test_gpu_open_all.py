@@ -6,7 +6,18 @@ Every comparison is bit-exact on canonical Montgomery affine words.  Expected va
 bbg_g1_fixed_base_mul and oracle.g1_mul, or from the existing single-opening route bbg_kate_opening + bbg_msm.  Where all n proofs by the
 model would take minutes (2^10: a million oracle multiplications) sixteen seeded indices are checked by it instead.
 
-The SRS is freed between prepare and the first call in every test: the handle keeps nothing of it."""
+The SRS is freed between prepare and the first call in every test: the handle keeps nothing of it.
+
+Designed inputs (sections 8 - 11, tests/tools/g1_design.py; tests/test_g1_design_cpu.py holds the designs to their claims).  Over a hashed or
+a random powers string no entry of s_hat = NTT_G1,2n(s^) is infinite and no entry of c_hat = NTT_Fr,2n(c^) is zero, so these cases build
+strings [a_j] G and coefficients whose transforms vanish at chosen indices, and want [k_m] G for the integers k_m = sum_j q^(m)_j a_j:
+  8   infinite entries of the prepared string: k_open_all_pointwise's aff_is_inf branch, k_ecntt_normalize<true>'s stored infinity, and
+      xyzz_mul_glv returning early in some lanes of a wave -- both ends, a wave border, a later round of the lane-stride loop;
+  9   zero entries of c_hat: the k = 0 path of xyzz_mul_glv among ordinary products, beside a finite and at an infinite s_hat entry;
+  10  powers strings of x = 1, -1, w_n, w_n^3, w_n^-1, w_2n with f = 1 + X + .., 1 - X + .., random: equal and opposite points meet inside
+      both sets of stages, which the pointwise products feed with non-normalised XYZZ (for f = 1 + X + .. and x on the domain all proofs
+      but two cancel to infinity inside the forward stages);
+  11  one handle through a random, a designed, the zero and the first polynomial again: nothing an early return leaves behind leaks."""
 import contextlib
 import ctypes
 import json
@@ -18,6 +29,7 @@ import numpy as np
 import pytest
 
 import coarse_inputs as ci
+import g1_design as gd
 import lagrange_model as lm
 import open_all_model as oa
 
@@ -310,3 +322,158 @@ def test_time_bound_at_2_12(bbg):
             if d is not None:
                 bbg.dev_free(d)
         srs.free()
+
+
+# ------------------------------------------------------------------------------------------------ designed inputs (g1_design.py)
+INF_AT = {2: {3}, 3: {0, 5, 15}, 6: {0, 1, 63, 64, 65, 127}, 8: {0, 1, 63, 64, 65, 130, 511}}  # where s_hat is the point at infinity
+# where c_hat is zero: at an infinite s_hat entry, at its finite neighbour, at 0 and at 2n - 1; at 2^8 also past the first 64 lanes,
+# at the infinite entry 130 and the finite 131
+ZERO_AT = {3: {0, 5, 6, 15}, 6: {0, 1, 2, 127}, 8: {0, 1, 2, 130, 131, 511}}
+LANES64 = ("batch_mul_lanes", 64, 1 << 17)
+SERIAL = ("ecntt_mul", 0, 1)
+
+
+def fixed(bbg, scalars):
+    """[k] G for plain integers k by bbg_g1_fixed_base_mul; k = 0 comes back as the affine encoding of infinity."""
+    out = bbg.g1_fixed_base_mul(mont(scalars))
+    for i, k in enumerate(scalars):
+        assert np.array_equal(out[i], oa.aff_infinity()) == (k % R == 0)
+    return out
+
+
+def optional(bbg, opt):
+    return option(bbg, *opt) if opt else contextlib.nullcontext()
+
+
+def sixteen(n, seed, must=()):
+    ms = list(dict.fromkeys([0, n - 1] + list(must)))
+    rng = np.random.default_rng(seed)
+    while len(ms) < min(16, n):
+        m = int(rng.integers(0, n))
+        if m not in ms:
+            ms.append(m)
+    return ms
+
+
+def by_generator(oracle, scalars):
+    G = oracle.g1_generator()
+    return oa.canon_points(oracle, np.stack([oracle.g1_mul(G, k) for k in mont(scalars)]))
+
+
+@pytest.fixture(scope="module")
+def designed_string(bbg):
+    """lg -> (scalars a, points [a_j] G) of the string whose s_hat is infinite at exactly INF_AT[lg], made on first use."""
+    made = {}
+
+    def get(lg):
+        if lg not in made:
+            a, s_hat = gd.design_string(lg, INF_AT[lg], SEED + 800 + lg)
+            assert {k for k, v in enumerate(s_hat) if v == 0} == INF_AT[lg]
+            pts = fixed(bbg, a)
+            # what prepare computes, through bbg_g1_ntt (the same load, stages and normalize<true>): [s_hat_k] G, infinite where designed
+            check(bbg.g1_ntt(oa.embedding(pts, [0] * (1 << lg))[0]), fixed(bbg, s_hat), f"2^{lg}: NTT_G1,2n(s^) of the designed string")
+            made[lg] = (a, pts)
+        return made[lg]
+    return get
+
+
+# 8 ------------------------------------------------------------------------------------------------ infinite entries of s_hat
+@pytest.mark.parametrize("lg,opt", [(2, None), (3, None), (6, None), (8, LANES64), (2, SERIAL)], ids=["4", "8", "64", "256-lanes64", "4-ecntt_mul0"])
+def test_infinite_entries_of_the_prepared_string(bbg, oracle, designed_string, lg, opt):
+    n = 1 << lg
+    a, pts = designed_string(lg)
+    f = coefficients(SEED + 810 + lg, n)
+    ks = gd.proof_scalars(f, a)
+    want = fixed(bbg, ks)
+    with optional(bbg, opt):
+        h = prepared(bbg, bbg.srs_register(pts), lg)
+        try:
+            got = h.open(mont(f))
+        finally:
+            h.free()
+    check(got, want, f"n = {n}, {opt}: s_hat infinite at {sorted(INF_AT[lg])}")
+    if n <= 8:
+        check(want, oa.open_all_definition(oracle, pts, f), f"n = {n}: [k_m] G against the definition")
+    else:
+        ms = sixteen(n, SEED + 811)
+        by_oracle = oa.open_all_definition(oracle, pts, f, ms) if n <= 64 else by_generator(oracle, [ks[m] for m in ms])
+        check(want[ms], by_oracle, f"n = {n}: [k_m] G against the oracle at {ms}")
+
+
+# 9 ------------------------------------------------------------------------------------------------ zero entries of c_hat
+@pytest.mark.parametrize("string,lg,opt", [("hashed", 3, None), ("hashed", 6, None), ("hashed", 3, SERIAL),
+                                           ("designed", 3, None), ("designed", 6, None), ("designed", 8, LANES64), ("designed", 3, SERIAL)],
+                         ids=["hashed-8", "hashed-64", "hashed-8-ecntt_mul0", "designed-8", "designed-64", "designed-256-lanes64", "designed-8-ecntt_mul0"])
+def test_zero_entries_of_the_transformed_coefficients(bbg, oracle, hashed, designed_string, string, lg, opt):
+    n = 1 << lg
+    f, c_hat = gd.design_coeffs(lg, ZERO_AT[lg], SEED + 820 + lg)
+    assert {k for k, v in enumerate(c_hat) if v == 0} == ZERO_AT[lg]
+    if string == "hashed":
+        pts = hashed(lg)[0]
+        want = None
+    else:
+        a, pts = designed_string(lg)
+        assert ZERO_AT[lg] & INF_AT[lg] and ZERO_AT[lg] - INF_AT[lg]  # 0 x infinity, and 0 x a finite point
+        want = fixed(bbg, gd.proof_scalars(f, a))
+    with optional(bbg, opt):
+        h = prepared(bbg, bbg.srs_register(pts), lg)
+        try:
+            got = h.open(mont(f))
+        finally:
+            h.free()
+    what = f"n = {n}, {string} string, {opt}: c_hat zero at {sorted(ZERO_AT[lg])}"
+    if want is not None:
+        check(got, want, what)
+    if n <= 8:
+        check(got, oa.open_all_definition(oracle, pts, f), what + ", against the definition")
+    elif n <= 64:
+        ms = sixteen(n, SEED + 821)
+        check(got[ms], oa.open_all_definition(oracle, pts, f, ms), what + f", against the definition at {ms}")
+
+
+# 10 ----------------------------------------------------------------------------------------------- degenerate powers strings
+def power_bases(lg):
+    w = ci.root_of_unity(lg)
+    return {"1": 1, "-1": R - 1, "w_n": w, "w_n^3": pow(w, 3, R), "w_n^-1": pow(w, R - 2, R), "w_2n": ci.root_of_unity(lg + 1)}
+
+
+@pytest.mark.parametrize("lg,names,polys,opt", [(6, ("1", "-1", "w_n", "w_n^3", "w_n^-1", "w_2n"), ("ones", "alternating", "random"), None),
+                                                (6, ("1", "-1", "w_n", "w_n^3", "w_n^-1", "w_2n"), ("ones", "alternating", "random"), SERIAL),
+                                                (8, ("w_n^3",), ("ones",), LANES64)], ids=["64", "64-ecntt_mul0", "256-lanes64"])
+def test_degenerate_powers_strings(bbg, lg, names, polys, opt):
+    n = 1 << lg
+    fs = {"ones": [1] * n, "alternating": [1, R - 1] * (n // 2), "random": coefficients(SEED + 830 + lg, n)}
+    for name in names:
+        x = power_bases(lg)[name]
+        a = [pow(x, j, R) for j in range(n)]
+        with optional(bbg, opt):
+            h = prepared(bbg, bbg.srs_synth_powers(mont([x])[0], n), lg)
+            try:
+                got = {p: h.open(mont(fs[p])) for p in polys}
+            finally:
+                h.free()
+        for p in polys:
+            ks = gd.proof_scalars(fs[p], a)
+            if p == "ones" and name in ("-1", "w_n", "w_n^3", "w_n^-1"):
+                assert sum(1 for k in ks if k == 0) == n - 2  # all but the proofs at 1 and at x
+            check(got[p], fixed(bbg, ks), f"2^{lg}, x = {name}, f = {p}, {opt}")
+
+
+# 11 ----------------------------------------------------------------------------------------------- one handle, degenerate calls between
+@pytest.mark.parametrize("opt", [None, SERIAL], ids=["default", "ecntt_mul0"])
+def test_reuse_after_degenerate_calls(bbg, designed_string, opt):
+    lg = 6
+    n = 1 << lg
+    a, pts = designed_string(lg)
+    f1 = coefficients(SEED + 840, n)
+    f2, _ = gd.design_coeffs(lg, ZERO_AT[lg], SEED + 841)
+    with optional(bbg, opt):
+        h = prepared(bbg, bbg.srs_register(pts), lg)
+        try:
+            first = h.open(mont(f1))
+            check(first, fixed(bbg, gd.proof_scalars(f1, a)), f"{opt}: a random f")
+            check(h.open(mont(f2)), fixed(bbg, gd.proof_scalars(f2, a)), f"{opt}: a designed f behind it")
+            check(h.open(mont([0] * n)), infinities(n), f"{opt}: f = 0 behind that")
+            check(h.open(mont(f1)), first, f"{opt}: the first f again")
+        finally:
+            h.free()
