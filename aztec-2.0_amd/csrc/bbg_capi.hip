@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <set>
 
 namespace bbg {
@@ -20,19 +21,42 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line)
     g_last_error = buf;
     return e == hipErrorOutOfMemory ? BBG_E_NOMEM : BBG_E_HIP;
 }
-int ensure_buffer(void** buf, size_t* have, size_t need)
+// the reduce streams and their events, whichever of them exist (a creation that failed half way leaves some): all handles null afterwards
+void msm_release_aux_streams(bbg_ctx* ctx)
 {
-    if (*have >= need && *buf) return BBG_OK;
-    if (*buf) {
-        BBG_HIP(hipDeviceSynchronize());
-        BBG_HIP(hipFree(*buf));
-        *buf = nullptr;
-        *have = 0;
+    for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
+        if (ctx->aux_streams[k]) (void)hipStreamDestroy(ctx->aux_streams[k]);
+        if (ctx->ev_acc[k]) (void)hipEventDestroy(ctx->ev_acc[k]);
+        if (ctx->ev_done[k]) (void)hipEventDestroy(ctx->ev_done[k]);
+        ctx->aux_streams[k] = nullptr;
+        ctx->ev_acc[k] = ctx->ev_done[k] = nullptr;
+        ctx->ev_done_valid[k] = false;
     }
-    BBG_HIP(hipMalloc(buf, need));
-    *have = need;
-    return BBG_OK;
+    ctx->aux_stream = nullptr;
 }
+static void prof_release_events(bbg_ctx* ctx)
+{
+    for (auto& kv : ctx->prof) {
+        for (auto e : kv.second.start) (void)hipEventDestroy(e);
+        for (auto e : kv.second.stop) (void)hipEventDestroy(e);
+    }
+    ctx->prof.clear();
+}
+namespace {
+// A temporary of one entry point, released when its scope ends: device memory, or pinned host memory (host = true)
+struct ScopedMem {
+    void* p = nullptr;
+    bool host = false;
+    ScopedMem() = default;
+    explicit ScopedMem(bool pinned) : host(pinned) {}
+    ScopedMem(const ScopedMem&) = delete;
+    ScopedMem& operator=(const ScopedMem&) = delete;
+    ~ScopedMem()
+    {
+        if (p) (void)(host ? hipHostFree(p) : hipFree(p));
+    }
+};
+} // namespace
 int srs_build_tables(const void* d_points, size_t n, void* d_table, int c, hipStream_t st);
 int msm_pick_window(const bbg_ctx* ctx, size_t n);
 void prover_report(const bbg_ctx* ctx, size_t* bytes, unsigned* count); // prover.hip: live bbg_prover handles of a context
@@ -86,6 +110,101 @@ static int make_srs(bbg_ctx* ctx, const void* d_plain_points, size_t n, bbg_srs*
     *out = s;
     return BBG_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ options (bbg_set_option)
+namespace {
+enum : unsigned {
+    OPT_SYNC = 1,         // the device is idle before the value changes
+    OPT_RELAYOUT = 2,     // the MSM arena is laid out again by the next MSM
+    OPT_DROP_DOMAINS = 4, // the cached NTT domains are freed after the value is stored: the next transform plans with it
+};
+enum OptStore { AS_VALUE, AS_BOOL, AS_LOW4 }; // (int)value, value != 0, value & 15
+constexpr long ANY_LO = std::numeric_limits<long>::min(), ANY_HI = std::numeric_limits<long>::max(); // every long is accepted
+struct Option {
+    const char* key;
+    int bbg_ctx::* field;
+    long lo, hi; // accepted range, both ends included
+    OptStore store;
+    unsigned effects;
+    // keys with a rule of their own, applied to a value inside the range before anything changes: BBG_OK, or the error with its text set
+    int (*rule)(bbg_ctx* ctx, long value) = nullptr;
+    long bbg_ctx::* wide = nullptr; // the one member that is a long (`field` is null then)
+};
+
+int opt_compiled_width(bbg_ctx*, long value)
+{
+    if (value == 0 || msm_width_slot((int)value) >= 0) return BBG_OK;
+    set_error("bbg_set_option: msm_window / prover_tail_window must be 0 (automatic) or a compiled width: 13, 16, 17, 19, 20, 22");
+    return BBG_E_INVALID;
+}
+int opt_multiple_of_64(bbg_ctx*, long value)
+{
+    if (value % 64 == 0) return BBG_OK;
+    set_error("bbg_set_option: batch_mul_lanes must be a multiple of 64 in 64 .. 2^20");
+    return BBG_E_INVALID;
+}
+int opt_library_sort(bbg_ctx*, long value)
+{
+#ifndef BBG_ROCPRIM_SORT
+    if (value == 0) { set_error("msm_sort = 0 (rocPRIM radix sort, A/B only) needs a library built with `make ROCPRIM_SORT=1`"); return BBG_E_INVALID; }
+#endif
+    (void)value;
+    return BBG_OK;
+}
+// fault injection is not an option of a production process: it exists only where the environment asked for test hooks when the process
+// started (BBG_TEST_HOOKS=1, read once) -- a stray option string cannot make a proof fail
+int opt_test_hook(bbg_ctx*, long)
+{
+    static const bool hooks = [] { const char* e = getenv("BBG_TEST_HOOKS"); return e && e[0] == '1' && e[1] == 0; }();
+    if (hooks) return BBG_OK;
+    set_error("bbg_set_option: prover_fail_round is a test hook (start the process with BBG_TEST_HOOKS=1)");
+    return BBG_E_INVALID;
+}
+// the priority is a property of the reduce streams: they go, with their events, once the device is idle (hence no OPT_SYNC on the
+// entry), and the next MSM creates them again
+int opt_release_aux_streams(bbg_ctx* ctx, long)
+{
+    BBG_HIP(hipDeviceSynchronize());
+    msm_release_aux_streams(ctx);
+    return BBG_OK;
+}
+
+const Option OPTIONS[] = {
+    // MSM
+    { "msm_async_reduce", &bbg_ctx::msm_async_reduce, ANY_LO, ANY_HI, AS_BOOL, OPT_SYNC },       // reduce phases on the auxiliary streams (bbg_join)
+    { "msm_reduce_priority", &bbg_ctx::msm_reduce_low_priority, ANY_LO, ANY_HI, AS_BOOL, 0, opt_release_aux_streams }, // 1 = low-priority reduce streams
+    { "msm_reduce_quad", &bbg_ctx::msm_reduce_quad, ANY_LO, ANY_HI, AS_LOW4, OPT_SYNC },         // bit mask: reduce stages with four lanes per EC operation
+    { "msm_acc_waves", &bbg_ctx::msm_acc_waves, ANY_LO, ANY_HI, AS_VALUE, OPT_SYNC | OPT_RELAYOUT }, // lane segments per SIMD lane, 0 = automatic
+    { "msm_sort", &bbg_ctx::msm_sort, 0, 1, AS_VALUE, OPT_SYNC, opt_library_sort },              // 1 = partition sort, 0 = rocPRIM radix sort
+    { "msm_limbs29", &bbg_ctx::msm_limbs29, ANY_LO, ANY_HI, AS_BOOL, 0 },                        // accumulation on 9 x 29-bit limbs
+    { "msm_accumulate_quad", &bbg_ctx::msm_accumulate_quad, ANY_LO, ANY_HI, AS_BOOL, 0 },        // small MSMs: four threads per lane segment
+    { "msm_upload_pieces", &bbg_ctx::msm_upload_pieces, 1, bbg_ctx::UPLOAD_PIECES, AS_VALUE, 0 }, // bbg_msm: pieces the host scalars travel in
+    { "msm_window", &bbg_ctx::msm_window, ANY_LO, ANY_HI, AS_VALUE, 0, opt_compiled_width },     // 0 = automatic, or a compiled width
+    // G1 batch multiplication and transforms
+    { "batch_mul_glv", &bbg_ctx::batch_mul_glv, 0, 1, AS_VALUE, 0 },                             // 1 = windowed GLV, 0 = bit-serial double-and-add
+    { "batch_mul_lanes", nullptr, 64, 1L << 20, AS_VALUE, 0, opt_multiple_of_64, &bbg_ctx::batch_mul_lanes }, // lanes = 1 KiB tables held; a launch-time choice
+    { "ecntt_mul", &bbg_ctx::ecntt_mul, 0, 1, AS_VALUE, 0 },                                     // the G1 transforms' stages: 1 = windowed GLV, 0 = bit-serial
+    // quotient, polynomials, prover
+    { "quotient_limbs29", &bbg_ctx::quotient_limbs29, ANY_LO, ANY_HI, AS_BOOL, 0 },              // widgets on lazily reduced 29-bit limbs
+    { "quotient_fuse", &bbg_ctx::quotient_fuse, ANY_LO, ANY_HI, AS_BOOL, 0 },                    // arithmetic + range + logic widgets in one pass
+    { "quotient_setup_plan", &bbg_ctx::quotient_setup_plan, 0, 1, AS_VALUE, 0 },                 // set-up blocks by the lanes of one wave
+    { "poly_limbs29", &bbg_ctx::poly_limbs29, 0, 1, AS_VALUE, 0 },                               // linear combinations / evaluations on 29-bit limbs
+    { "prover_fused_divide", &bbg_ctx::prover_fused_divide, 0, 1, AS_VALUE, 0 },                 // round 4 divides inside the coset iFFT's first load
+    { "prover_tail_window", &bbg_ctx::prover_tail_window, ANY_LO, ANY_HI, AS_VALUE, 0, opt_compiled_width }, // width of the round-ending commitments
+    { "prover_ntt_batch", &bbg_ctx::prover_ntt_batch, ANY_LO, ANY_HI, AS_BOOL, 0 },              // the wires' transforms through one launch set
+    { "prover_msm_batch", &bbg_ctx::prover_msm_batch, 0, BBG_MSM_BATCH_MAX, AS_VALUE, 0 },       // commitments of a round per launch set
+    { "prover_early_cosets", &bbg_ctx::prover_early_cosets, -1, 1, AS_VALUE, 0 },                // -1 = automatic (from 2^18 gates)
+    { "prover_fail_round", &bbg_ctx::prover_fail_round, ANY_LO, ANY_HI, AS_VALUE, 0, opt_test_hook }, // tests only: the next call of this round fails once
+    // NTT: the first two are launch-time choices between kernels over the same plan and tables, the others change the plan
+    { "ntt_limbs29", &bbg_ctx::ntt_limbs29, -1, 1, AS_VALUE, 0 },                                // -1 = automatic
+    { "ntt_lds_planes", &bbg_ctx::ntt_lds_planes, 0, 2, AS_VALUE, 0 },                           // 0 = automatic
+    { "ntt_tile_log", &bbg_ctx::ntt_tile_log, 9, 12, AS_VALUE, OPT_DROP_DOMAINS },               // log2(elements per LDS tile)
+    { "ntt_kernel", &bbg_ctx::ntt_kernel, 1, 2, AS_VALUE, OPT_DROP_DOMAINS },                    // 2 = radix-8 passes in registers, 1 = radix 2 in LDS
+    { "ntt_big_tile", &bbg_ctx::ntt_big_tile, 0, 3, AS_VALUE, OPT_DROP_DOMAINS },                // 4096-element tiles for 2^21 (1), 2^22 as well (2)
+    { "ntt_max_logr8", &bbg_ctx::ntt_max_logr8, 6, 11, AS_VALUE, OPT_DROP_DOMAINS },             // max log-radix per radix-8 pass
+    { "ntt_max_logr", &bbg_ctx::ntt_max_logr, 4, 10, AS_VALUE, OPT_DROP_DOMAINS },               // max log-radix per radix-2 pass
+};
+} // namespace
 } // namespace bbg
 
 using namespace bbg;
@@ -140,29 +259,13 @@ void bbg_destroy(bbg_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     for (auto& kv : ctx->domains) ntt_free_domain(kv.second);
-    for (auto& kv : ctx->prof) {
-        for (auto e : kv.second.start) (void)hipEventDestroy(e);
-        for (auto e : kv.second.stop) (void)hipEventDestroy(e);
-    }
+    prof_release_events(ctx);
     for (auto& kv : ctx->dpv_consts) (void)hipFree(kv.second);
     for (auto& kv : ctx->dpv_tables) (void)hipFree(kv.second);
-    if (ctx->ntt_scratch) (void)hipFree(ctx->ntt_scratch);
-    if (ctx->quot_setup) (void)hipFree(ctx->quot_setup);
-    if (ctx->gp_totals) (void)hipFree(ctx->gp_totals);
-    if (ctx->staging) (void)hipFree(ctx->staging);
-    if (ctx->msm.buf) (void)hipFree(ctx->msm.buf);
-    if (ctx->msm_tiny.buf) (void)hipFree(ctx->msm_tiny.buf);
-    if (ctx->poly_scratch) (void)hipFree(ctx->poly_scratch);
-    if (ctx->fb_table) (void)hipFree(ctx->fb_table);
-    if (ctx->vb_tables) (void)hipFree(ctx->vb_tables);
-    if (ctx->ecntt_work) (void)hipFree(ctx->ecntt_work);
-    if (ctx->aux_stream) {
-        for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
-            (void)hipStreamDestroy(ctx->aux_streams[k]);
-            (void)hipEventDestroy(ctx->ev_acc[k]);
-            (void)hipEventDestroy(ctx->ev_done[k]);
-        }
-    }
+    for (auto b : BBG_CTX_SCRATCH) (ctx->*b).release();
+    ctx->msm.release();
+    ctx->msm_tiny.release();
+    msm_release_aux_streams(ctx);
     if (ctx->upload_stream) {
         (void)hipStreamDestroy(ctx->upload_stream);
         (void)hipEventDestroy(ctx->ev_upload_go);
@@ -217,162 +320,25 @@ int bbg_set_option(bbg_ctx* ctx, const char* key, long value)
     CHECK_CTX(ctx);
     if (!key) { set_error("bbg_set_option: null key"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!strcmp(key, "msm_async_reduce")) {
-        BBG_HIP(hipDeviceSynchronize());
-        ctx->msm_async_reduce = value != 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_reduce_priority")) { // 1 = low-priority auxiliary stream (default), 0 = normal; takes effect when the stream is (re)created
-        BBG_HIP(hipDeviceSynchronize());
-        ctx->msm_reduce_low_priority = value != 0;
-        if (ctx->aux_stream) {
-            for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
-                (void)hipStreamDestroy(ctx->aux_streams[k]);
-                ctx->aux_streams[k] = nullptr;
-                (void)hipEventDestroy(ctx->ev_acc[k]);
-                (void)hipEventDestroy(ctx->ev_done[k]);
-                ctx->ev_done_valid[k] = false;
-            }
-            ctx->aux_stream = nullptr;
-        }
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_upload_pieces")) { // bbg_msm: pieces the host scalars travel in (1 = one copy in front of the MSM)
-        if (value < 1 || value > bbg_ctx::UPLOAD_PIECES) { set_error("bbg_set_option: msm_upload_pieces must be 1..4"); return BBG_E_INVALID; }
-        ctx->msm_upload_pieces = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "batch_mul_glv")) { // bbg_g1_batch_mul: 1 = windowed GLV, 0 = bit-serial double-and-add (A/B)
-        if (value != 0 && value != 1) { set_error("batch_mul_glv: 0 or 1"); return BBG_E_INVALID; }
-        ctx->batch_mul_glv = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "ecntt_mul")) { // bbg_srs_lagrange: 1 = the stages multiply with the windowed GLV form, 0 = bit-serial (A/B)
-        if (value != 0 && value != 1) { set_error("ecntt_mul: 0 or 1"); return BBG_E_INVALID; }
-        ctx->ecntt_mul = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "batch_mul_lanes")) { // lanes of the variable-base kernels = 1 KiB tables held; a launch-time choice
-        if (value < 64 || value > (1L << 20) || value % 64) { set_error("batch_mul_lanes: a multiple of 64 in 64 .. 2^20"); return BBG_E_INVALID; }
-        ctx->batch_mul_lanes = value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_reduce_quad")) {
-        BBG_HIP(hipDeviceSynchronize());
-        ctx->msm_reduce_quad = (int)value & 15;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_acc_waves")) {
-        BBG_HIP(hipDeviceSynchronize());
-        ctx->msm_acc_waves = (int)value;
-        ctx->msm_layout_n = 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_limbs29")) {
-        ctx->msm_limbs29 = value != 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_accumulate_quad")) {
-        ctx->msm_accumulate_quad = value != 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "prover_msm_batch")) {
-        if (value < 0 || value > BBG_MSM_BATCH_MAX) { set_error("prover_msm_batch must be 0 .. BBG_MSM_BATCH_MAX"); return BBG_E_INVALID; }
-        ctx->prover_msm_batch = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "prover_early_cosets")) {
-        if (value < -1 || value > 1) { set_error("prover_early_cosets: -1 (automatic), 0 or 1"); return BBG_E_INVALID; }
-        ctx->prover_early_cosets = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "quotient_setup_plan")) {
-        if (value != 0 && value != 1) { set_error("quotient_setup_plan: 0 or 1"); return BBG_E_INVALID; }
-        ctx->quotient_setup_plan = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "poly_limbs29")) {
-        if (value != 0 && value != 1) { set_error("poly_limbs29: 0 or 1"); return BBG_E_INVALID; }
-        ctx->poly_limbs29 = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "prover_fused_divide")) {
-        if (value != 0 && value != 1) { set_error("prover_fused_divide: 0 or 1"); return BBG_E_INVALID; }
-        ctx->prover_fused_divide = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "prover_tail_window")) {
-        if (value != 0 && msm_width_slot((int)value) < 0) { set_error("prover_tail_window: 0 or a compiled window width"); return BBG_E_INVALID; }
-        ctx->prover_tail_window = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "prover_ntt_batch")) {
-        ctx->prover_ntt_batch = value != 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "prover_fail_round")) { // tests only: the next call of this prover round (1, 3, 4, 5, 6) fails once, as a device error would
-        // fault injection is not an option of a production process: it exists only where the environment asked for test hooks when the
-        // process started (BBG_TEST_HOOKS=1, read once) -- a stray option string cannot make a proof fail (round-5 advisor finding)
-        static const bool hooks = [] { const char* e = getenv("BBG_TEST_HOOKS"); return e && e[0] == '1' && e[1] == 0; }();
-        if (!hooks) { set_error("bbg_set_option: prover_fail_round is a test hook (start the process with BBG_TEST_HOOKS=1)"); return BBG_E_INVALID; }
-        ctx->prover_fail_round = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "quotient_limbs29")) {
-        ctx->quotient_limbs29 = value != 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "quotient_fuse")) {
-        ctx->quotient_fuse = value != 0;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_window")) {
-        if (value != 0 && msm_width_slot((int)value) < 0) { set_error("msm_window must be 0 (automatic) or a compiled width: 13, 16, 17, 19, 20, 22"); return BBG_E_INVALID; }
-        ctx->msm_window = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "msm_sort")) {
-        if (value != 0 && value != 1) { set_error("msm_sort must be 0 or 1"); return BBG_E_INVALID; }
-#ifndef BBG_ROCPRIM_SORT
-        if (value == 0) { set_error("msm_sort = 0 (rocPRIM radix sort, A/B only) needs a library built with `make ROCPRIM_SORT=1`"); return BBG_E_INVALID; }
-#endif
-        BBG_HIP(hipDeviceSynchronize());
-        ctx->msm_sort = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "ntt_limbs29")) { // a launch-time choice between kernels over the same plan and tables
-        if (value < -1 || value > 1) { set_error("ntt_limbs29 must be -1 (automatic), 0 or 1"); return BBG_E_INVALID; }
-        ctx->ntt_limbs29 = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "ntt_lds_planes")) { // a launch-time choice between two kernels over the same plan: no domain is rebuilt
-        if (value < 0 || value > 2) { set_error("ntt_lds_planes must be 0 (automatic), 1 or 2"); return BBG_E_INVALID; }
-        ctx->ntt_lds_planes = (int)value;
-        return BBG_OK;
-    }
-    if (!strcmp(key, "ntt_tile_log")) {
-        if (value < 9 || value > 12) { set_error("ntt_tile_log must be 9..12"); return BBG_E_INVALID; }
-        ctx->ntt_tile_log = (int)value;
-    } else if (!strcmp(key, "ntt_kernel")) {
-        if (value != 1 && value != 2) { set_error("ntt_kernel must be 1 or 2"); return BBG_E_INVALID; }
-        ctx->ntt_kernel = (int)value;
-    } else if (!strcmp(key, "ntt_big_tile")) {
-        if (value < 0 || value > 3) { set_error("ntt_big_tile must be 0 .. 3"); return BBG_E_INVALID; }
-        ctx->ntt_big_tile = (int)value;
-    } else if (!strcmp(key, "ntt_max_logr8")) {
-        if (value < 6 || value > 11) { set_error("ntt_max_logr8 must be 6..11"); return BBG_E_INVALID; }
-        ctx->ntt_max_logr8 = (int)value;
-    } else if (!strcmp(key, "ntt_max_logr")) {
-        if (value < 4 || value > 10) { set_error("ntt_max_logr must be 4..10"); return BBG_E_INVALID; }
-        ctx->ntt_max_logr = (int)value;
-    } else {
-        set_error(std::string("bbg_set_option: unknown key ") + key);
+    const Option* o = std::find_if(std::begin(OPTIONS), std::end(OPTIONS), [&](const Option& x) { return !strcmp(x.key, key); });
+    if (o == std::end(OPTIONS)) { set_error(std::string("bbg_set_option: unknown key ") + key); return BBG_E_INVALID; }
+    if (value < o->lo || value > o->hi) {
+        set_error(std::string("bbg_set_option: ") + key + " must be in " + std::to_string(o->lo) + " .. " + std::to_string(o->hi));
         return BBG_E_INVALID;
     }
-    // plans are per domain: drop cached domains so the new plan takes effect
-    BBG_HIP(hipDeviceSynchronize());
-    for (auto& kv : ctx->domains) ntt_free_domain(kv.second);
-    ctx->domains.clear();
+    if (o->rule) {
+        int rc = o->rule(ctx, value);
+        if (rc) return rc;
+    }
+    if (o->effects & OPT_SYNC) BBG_HIP(hipDeviceSynchronize());
+    if (o->wide) ctx->*o->wide = value;
+    else ctx->*o->field = o->store == AS_BOOL ? value != 0 : o->store == AS_LOW4 ? (int)value & 15 : (int)value;
+    if (o->effects & OPT_RELAYOUT) ctx->msm_layout_n = 0;
+    if (o->effects & OPT_DROP_DOMAINS) { // plans are per domain: drop cached domains so the new plan takes effect
+        BBG_HIP(hipDeviceSynchronize());
+        for (auto& kv : ctx->domains) ntt_free_domain(kv.second);
+        ctx->domains.clear();
+    }
     return BBG_OK;
 }
 
@@ -399,8 +365,8 @@ int bbg_memory_report(bbg_ctx* ctx, bbg_memory_info* out)
     }
     for (const auto& kv : ctx->dpv_tables) out->ntt_tables += (size_t)32 << ((kv.first >> 8) & 0xff); // poly_dpv_table: one Fr per target-domain point
     out->msm_arena = ctx->msm.bytes + ctx->msm_tiny.bytes;
-    out->scratch = ctx->ntt_scratch_bytes + ctx->staging_bytes + ctx->poly_scratch_bytes + ctx->gp_totals_bytes + ctx->quot_setup_bytes +
-                   ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES + ctx->fb_table_bytes + ctx->vb_tables_bytes + ctx->ecntt_work_bytes;
+    out->scratch = ctx->dpv_consts.size() * (size_t)DPV_CONSTS_BYTES;
+    for (auto b : BBG_CTX_SCRATCH) out->scratch += (ctx->*b).bytes;
     prover_report(ctx, &out->prover_keys, &out->live_provers);
     out->total = out->srs_points + out->srs_tables + out->ntt_tables + out->msm_arena + out->scratch + out->prover_keys;
     BBG_HIP(hipMemGetInfo(&out->device_free, &out->device_total));
@@ -422,22 +388,10 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released)
         ctx->dpv_consts.clear();
         for (auto& kv : ctx->dpv_tables) (void)hipFree(kv.second);
         ctx->dpv_tables.clear();
-        auto drop = [](void** buf, size_t* bytes) {
-            if (*buf) (void)hipFree(*buf);
-            *buf = nullptr;
-            *bytes = 0;
-        };
-        drop(&ctx->ntt_scratch, &ctx->ntt_scratch_bytes);
-        drop(&ctx->staging, &ctx->staging_bytes);
-        drop(&ctx->poly_scratch, &ctx->poly_scratch_bytes);
-        drop(&ctx->gp_totals, &ctx->gp_totals_bytes);
-        drop(&ctx->quot_setup, &ctx->quot_setup_bytes);
-        drop(&ctx->fb_table, &ctx->fb_table_bytes); // the next fixed-base call rebuilds it
-        ctx->fb_table_valid = false;
-        drop(&ctx->vb_tables, &ctx->vb_tables_bytes);
-        drop(&ctx->ecntt_work, &ctx->ecntt_work_bytes);
-        drop(&ctx->msm.buf, &ctx->msm.bytes);
-        drop(&ctx->msm_tiny.buf, &ctx->msm_tiny.bytes);
+        for (auto b : BBG_CTX_SCRATCH) (ctx->*b).release();
+        ctx->fb_table_valid = false; // the next fixed-base call rebuilds the table
+        ctx->msm.release();
+        ctx->msm_tiny.release();
         ctx->msm_tiny_layout = 0;
         ctx->msm_layout_n = 0; // the arena's counters are re-initialised with the next layout
         ctx->msm_zero_buf = nullptr;
@@ -472,11 +426,7 @@ int bbg_profile_enable(bbg_ctx* ctx, int on)
     CHECK_CTX(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
     BBG_HIP(hipStreamSynchronize(ctx->stream));
-    for (auto& kv : ctx->prof) {
-        for (auto e : kv.second.start) (void)hipEventDestroy(e);
-        for (auto e : kv.second.stop) (void)hipEventDestroy(e);
-    }
-    ctx->prof.clear();
+    prof_release_events(ctx);
     ctx->prof_on = on != 0;
     return BBG_OK;
 }
@@ -538,17 +488,15 @@ int bbg_srs_register(bbg_ctx* ctx, const uint64_t* points, size_t n, size_t stri
         return BBG_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void* d_plain = nullptr;
-    BBG_HIP(hipMalloc(&d_plain, n ? n * 64 : 64));
+    ScopedMem d_plain;
+    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
     hipError_t e;
     if (stride_bytes == 64)
-        e = hipMemcpyAsync(d_plain, points, n * 64, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(d_plain.p, points, n * 64, hipMemcpyHostToDevice, ctx->stream);
     else
-        e = hipMemcpy2DAsync(d_plain, 64, points, 128, 64, n, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(d_plain); return hip_fail(e, "SRS upload", __FILE__, __LINE__); }
-    int rc = make_srs(ctx, d_plain, n, out);
-    (void)hipFree(d_plain);
-    return rc;
+        e = hipMemcpy2DAsync(d_plain.p, 64, points, 128, 64, n, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "SRS upload", __FILE__, __LINE__);
+    return make_srs(ctx, d_plain.p, n, out);
 }
 
 int bbg_srs_register_device(bbg_ctx* ctx, const void* d_points, size_t n, bbg_srs** out)
@@ -565,11 +513,10 @@ int bbg_srs_synth_linear(bbg_ctx* ctx, uint64_t a, uint64_t s, size_t n, bbg_srs
     if (!out) { set_error("bbg_srs_synth_linear: null out"); return BBG_E_INVALID; }
     if (s == 0 || a == 0) { set_error("bbg_srs_synth_linear: a and s must be non-zero"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void* d_plain = nullptr;
-    BBG_HIP(hipMalloc(&d_plain, n ? n * 64 : 64));
-    int rc = srs_synth_linear(ctx, a, s, n, d_plain, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, out);
-    (void)hipFree(d_plain);
+    ScopedMem d_plain;
+    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
+    int rc = srs_synth_linear(ctx, a, s, n, d_plain.p, ctx->stream);
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, n, out);
     return rc;
 }
 
@@ -578,11 +525,10 @@ int bbg_srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, bbg_srs** out)
     CHECK_CTX(ctx);
     if (!out) { set_error("bbg_srs_synth_hashed: null out"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void* d_plain = nullptr;
-    BBG_HIP(hipMalloc(&d_plain, n ? n * 64 : 64));
-    int rc = srs_synth_hashed(ctx, seed, n, d_plain, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, out);
-    (void)hipFree(d_plain);
+    ScopedMem d_plain;
+    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
+    int rc = srs_synth_hashed(ctx, seed, n, d_plain.p, ctx->stream);
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, n, out);
     return rc;
 }
 
@@ -599,20 +545,14 @@ int bbg_srs_synth_powers(bbg_ctx* ctx, const uint64_t x[4], size_t n, bbg_srs** 
         return BBG_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void *d_plain = nullptr, *d_pow = nullptr;
-    bbg_srs* res = nullptr;
-    int rc = BBG_OK;
-    hipError_t e = hipMalloc(&d_plain, n * 64);
-    if (e == hipSuccess) e = hipMalloc(&d_pow, n * 32);
-    if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_synth_powers: working set", __FILE__, __LINE__);
-    if (rc == BBG_OK) rc = fixed_base_powers(x, n, d_pow, ctx->stream);
-    if (rc == BBG_OK) rc = fixed_base_mul(ctx, nullptr, d_pow, n, d_plain, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
-    if (d_pow) (void)hipFree(d_pow);
-    if (d_plain) (void)hipFree(d_plain);
+    ScopedMem d_plain, d_pow;
+    hipError_t e = hipMalloc(&d_plain.p, n * 64);
+    if (e == hipSuccess) e = hipMalloc(&d_pow.p, n * 32);
+    if (e != hipSuccess) return hip_fail(e, "bbg_srs_synth_powers: working set", __FILE__, __LINE__);
+    int rc = fixed_base_powers(x, n, d_pow.p, ctx->stream);
+    if (rc == BBG_OK) rc = fixed_base_mul(ctx, nullptr, d_pow.p, n, d_plain.p, ctx->stream);
     if (rc) return rc;
-    *out = res;
-    return BBG_OK;
+    return make_srs(ctx, d_plain.p, n, out); // window tables + the synchronisation
 }
 
 // The update step of a powers-of-x string, P_i' = [y^i] P_i: the powers y^i on the device (k_fb_powers), the variable-base batch
@@ -631,20 +571,14 @@ int bbg_srs_scale_powers(bbg_ctx* ctx, bbg_srs* srs, const uint64_t y[4], bbg_sr
     const size_t n = srs->s.n;
     if (n == 0) { set_error("bbg_srs_scale_powers: the SRS is empty"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void *d_plain = nullptr, *d_pow = nullptr;
-    bbg_srs* res = nullptr;
-    int rc = BBG_OK;
-    hipError_t e = hipMalloc(&d_plain, n * 64);
-    if (e == hipSuccess) e = hipMalloc(&d_pow, n * 32);
-    if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_scale_powers: working set", __FILE__, __LINE__);
-    if (rc == BBG_OK) rc = fixed_base_powers(y, n, d_pow, ctx->stream);
-    if (rc == BBG_OK) rc = var_base_mul(ctx, srs->s.points, d_pow, n, 0, d_plain, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
-    if (d_pow) (void)hipFree(d_pow);
-    if (d_plain) (void)hipFree(d_plain);
+    ScopedMem d_plain, d_pow;
+    hipError_t e = hipMalloc(&d_plain.p, n * 64);
+    if (e == hipSuccess) e = hipMalloc(&d_pow.p, n * 32);
+    if (e != hipSuccess) return hip_fail(e, "bbg_srs_scale_powers: working set", __FILE__, __LINE__);
+    int rc = fixed_base_powers(y, n, d_pow.p, ctx->stream);
+    if (rc == BBG_OK) rc = var_base_mul(ctx, srs->s.points, d_pow.p, n, 0, d_plain.p, ctx->stream);
     if (rc) return rc;
-    *out = res;
-    return BBG_OK;
+    return make_srs(ctx, d_plain.p, n, out); // window tables + the synchronisation
 }
 
 // pts: num_points x 8 limbs in STANDARD (non-Montgomery) form, slot 0 free: sets monomials[0] = G = (1, 2), converts to Montgomery form
@@ -655,13 +589,12 @@ static int srs_from_plain_points(bbg_ctx* ctx, std::vector<uint64_t>& pts, size_
     pts[0] = 1;
     pts[4] = 2;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void* d_plain = nullptr;
-    BBG_HIP(hipMalloc(&d_plain, num_points * 64));
-    hipError_t e = hipMemcpyAsync(d_plain, pts.data(), num_points * 64, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(d_plain); return hip_fail(e, "transcript upload", __FILE__, __LINE__); }
-    int rc = field_op_device(1, 5 /* to_montgomery */, d_plain, nullptr, d_plain, num_points * 2, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, num_points, out);
-    (void)hipFree(d_plain);
+    ScopedMem d_plain;
+    BBG_HIP(hipMalloc(&d_plain.p, num_points * 64));
+    hipError_t e = hipMemcpyAsync(d_plain.p, pts.data(), num_points * 64, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "transcript upload", __FILE__, __LINE__);
+    int rc = field_op_device(1, 5 /* to_montgomery */, d_plain.p, nullptr, d_plain.p, num_points * 2, ctx->stream);
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, num_points, out);
     return rc;
 }
 
@@ -816,14 +749,12 @@ int bbg_srs_write_transcript(bbg_srs* srs, const char* dir, size_t points_per_fi
     std::vector<uint64_t> plain(total * 8);
     {
         std::lock_guard<std::mutex> lk(srs->ctx->mu);
-        void* d_plain = nullptr;
-        BBG_HIP(hipMalloc(&d_plain, total * 64));
-        int rc = field_op_device(1, 4 /* from_montgomery */, (const char*)srs->s.points + 64, nullptr, d_plain, total * 2, srs->ctx->stream);
-        hipError_t e = hipSuccess;
-        if (rc == BBG_OK) e = hipMemcpyAsync(plain.data(), d_plain, total * 64, hipMemcpyDeviceToHost, srs->ctx->stream);
-        if (rc == BBG_OK && e == hipSuccess) e = hipStreamSynchronize(srs->ctx->stream);
-        (void)hipFree(d_plain);
+        ScopedMem d_plain;
+        BBG_HIP(hipMalloc(&d_plain.p, total * 64));
+        int rc = field_op_device(1, 4 /* from_montgomery */, (const char*)srs->s.points + 64, nullptr, d_plain.p, total * 2, srs->ctx->stream);
         if (rc) return rc;
+        hipError_t e = hipMemcpyAsync(plain.data(), d_plain.p, total * 64, hipMemcpyDeviceToHost, srs->ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(srs->ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "transcript download", __FILE__, __LINE__);
     }
     for (auto& limb : plain) limb = __builtin_bswap64(limb);
@@ -877,32 +808,27 @@ int bbg_srs_lagrange(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, bbg_srs** out)
     if (n > srs->s.n) { set_error("bbg_srs_lagrange: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
     if (srs->s.device != ctx->device) { set_error("bbg_srs_lagrange: the SRS lives on another device than the context"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    void *d_work = nullptr, *d_plain = nullptr;
-    unsigned* d_flag = nullptr;
-    unsigned* h_flag = nullptr; // pinned: the copy behind the kernels stays asynchronous
     bbg_srs* res = nullptr;
-    int rc = BBG_OK;
-    hipError_t e = hipMalloc(&d_work, n * 128);
-    if (e == hipSuccess) e = hipMalloc(&d_plain, n * 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_flag, sizeof(unsigned));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h_flag, sizeof(unsigned), hipHostMallocDefault);
-    if (e == hipSuccess) {
-        *h_flag = 1; // stays set unless the copy below has run
-        e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), ctx->stream);
+    bool inf = false;
+    {
+        ScopedMem d_work, d_plain, d_flag, h_flag(true); // the flag word is pinned: the copy behind the kernels stays asynchronous
+        hipError_t e = hipMalloc(&d_work.p, n * 128);
+        if (e == hipSuccess) e = hipMalloc(&d_plain.p, n * 64);
+        if (e == hipSuccess) e = hipMalloc(&d_flag.p, sizeof(unsigned));
+        if (e == hipSuccess) e = hipHostMalloc(&h_flag.p, sizeof(unsigned), hipHostMallocDefault);
+        if (e == hipSuccess) {
+            *(unsigned*)h_flag.p = 1; // stays set unless the copy below has run
+            e = hipMemsetAsync(d_flag.p, 0, sizeof(unsigned), ctx->stream);
+        }
+        if (e != hipSuccess) return hip_fail(e, "bbg_srs_lagrange: working set", __FILE__, __LINE__);
+        int rc = ecntt_run(ctx, srs->s.points, log2n, 1, d_work.p, d_plain.p, (unsigned*)d_flag.p, ctx->stream);
+        if (rc) return rc;
+        e = hipMemcpyAsync(h_flag.p, d_flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "bbg_srs_lagrange: flag copy", __FILE__, __LINE__);
+        rc = make_srs(ctx, d_plain.p, n, &res); // window tables + the synchronisation
+        if (rc) return rc;
+        inf = *(unsigned*)h_flag.p != 0; // read before the temporaries go
     }
-    if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_lagrange: working set", __FILE__, __LINE__);
-    if (rc == BBG_OK) rc = ecntt_run(ctx, srs->s.points, log2n, 1, d_work, d_plain, d_flag, ctx->stream);
-    if (rc == BBG_OK) {
-        e = hipMemcpyAsync(h_flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "bbg_srs_lagrange: flag copy", __FILE__, __LINE__);
-    }
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain, n, &res); // window tables + the synchronisation
-    const bool inf = rc == BBG_OK && *h_flag != 0;
-    if (d_work) (void)hipFree(d_work);
-    if (d_plain) (void)hipFree(d_plain);
-    if (d_flag) (void)hipFree(d_flag);
-    if (h_flag) (void)hipHostFree(h_flag);
-    if (rc) return rc;
     if (inf) {
         bbg_srs_free(res);
         set_error("bbg_srs_lagrange: the transform has a point at infinity among its outputs (linearly dependent input points); an SRS cannot hold one");
@@ -919,9 +845,9 @@ int bbg_g1_ntt_device(bbg_ctx* ctx, const void* d_points_affine, unsigned log2n,
     if (!d_points_affine || !d_out_affine) { set_error("bbg_g1_ntt_device: null argument"); return BBG_E_INVALID; }
     if (log2n < 1 || log2n > 28) { set_error("bbg_g1_ntt_device: log2n must be 1 .. 28"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->ecntt_work, &ctx->ecntt_work_bytes, ((size_t)1 << log2n) * 128);
+    int rc = ctx->ecntt_work.ensure(((size_t)1 << log2n) * 128);
     if (rc) return rc;
-    return ecntt_run(ctx, d_points_affine, log2n, inverse, ctx->ecntt_work, d_out_affine, nullptr, ctx->stream);
+    return ecntt_run(ctx, d_points_affine, log2n, inverse, ctx->ecntt_work.p, d_out_affine, nullptr, ctx->stream);
 }
 
 int bbg_g1_ntt(bbg_ctx* ctx, const uint64_t* points_affine, unsigned log2n, int inverse, uint64_t* out_affine)
@@ -931,13 +857,13 @@ int bbg_g1_ntt(bbg_ctx* ctx, const uint64_t* points_affine, unsigned log2n, int 
     if (log2n < 1 || log2n > 28) { set_error("bbg_g1_ntt: log2n must be 1 .. 28"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << log2n;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 64);
-    if (rc == BBG_OK) rc = ensure_buffer(&ctx->ecntt_work, &ctx->ecntt_work_bytes, n * 128);
+    int rc = ctx->staging.ensure(n * 64);
+    if (rc == BBG_OK) rc = ctx->ecntt_work.ensure(n * 128);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    rc = ecntt_run(ctx, ctx->staging, log2n, inverse, ctx->ecntt_work, ctx->staging, nullptr, ctx->stream); // transformed in place
+    BBG_HIP(hipMemcpyAsync(ctx->staging.p, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    rc = ecntt_run(ctx, ctx->staging.p, log2n, inverse, ctx->ecntt_work.p, ctx->staging.p, nullptr, ctx->stream); // transformed in place
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, ctx->staging, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(out_affine, ctx->staging.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
@@ -969,9 +895,9 @@ int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_a
     CHECK_CTX(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << h->log2n;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 96);
+    int rc = ctx->staging.ensure(n * 96);
     if (rc) return rc;
-    char* st = (char*)ctx->staging; // proofs | coefficients
+    char* st = (char*)ctx->staging.p; // proofs | coefficients
     BBG_HIP(hipMemcpyAsync(st + n * 64, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = open_all_run(h, st + n * 64, st, ctx->stream);
     if (rc) return rc;
@@ -1047,9 +973,9 @@ int bbg_msm_batch(bbg_ctx* ctx, bbg_srs* srs, size_t count, const uint64_t* cons
         total += n[k];
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, total * 32 + 1024);
+    int rc = ctx->staging.ensure(total * 32 + 1024);
     if (rc) return rc;
-    char* st = (char*)ctx->staging; // results (count x 96 B <= 768 B) | scalars of MSM 0 | MSM 1 | ...
+    char* st = (char*)ctx->staging.p; // results (count x 96 B <= 768 B) | scalars of MSM 0 | MSM 1 | ...
     const void* d_ptrs[BBG_MSM_BATCH_MAX];
     size_t at = 1024;
     for (size_t k = 0; k < count; k++) {
@@ -1084,9 +1010,9 @@ int bbg_msm(bbg_ctx* ctx, bbg_srs* srs, const uint64_t* scalars, size_t from, si
     CHECK_CTX(ctx);
     if (!srs || (!scalars && n) || !out_jacobian) { set_error("bbg_msm: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 32 + 256);
+    int rc = ctx->staging.ensure(n * 32 + 256);
     if (rc) return rc;
-    char* st = (char*)ctx->staging;
+    char* st = (char*)ctx->staging.p;
     rc = msm_run(ctx, srs->s, st + 256, from, n, st, ctx->stream, scalars); // uploads the scalars itself, in pieces, under its first pass
     if (rc) return rc;
     rc = msm_join(ctx, ctx->stream);
@@ -1101,9 +1027,9 @@ int bbg_g1_sum(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t out_j
     CHECK_CTX(ctx);
     if ((!jacobians && n) || !out_jacobian) { set_error("bbg_g1_sum: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 96 + 256);
+    int rc = ctx->staging.ensure(n * 96 + 256);
     if (rc) return rc;
-    char* st = (char*)ctx->staging;
+    char* st = (char*)ctx->staging.p;
     if (n) BBG_HIP(hipMemcpyAsync(st + 256, jacobians, n * 96, hipMemcpyHostToDevice, ctx->stream));
     rc = g1_sum_device(ctx, st + 256, n, st, ctx->stream);
     if (rc) return rc;
@@ -1126,9 +1052,9 @@ int bbg_g1_normalize(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t
     if ((!jacobians || !out_affine) && n) { set_error("bbg_g1_normalize: null argument"); return BBG_E_INVALID; }
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 160);
+    int rc = ctx->staging.ensure(n * 160);
     if (rc) return rc;
-    char* st = (char*)ctx->staging;
+    char* st = (char*)ctx->staging.p;
     BBG_HIP(hipMemcpyAsync(st, jacobians, n * 96, hipMemcpyHostToDevice, ctx->stream));
     rc = g1_normalize_device(st, n, st + n * 96, ctx->stream);
     if (rc) return rc;
@@ -1150,9 +1076,9 @@ int bbg_g1_fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint6
     CHECK_CTX(ctx);
     if ((!scalars || !out_affine) && n) { set_error("bbg_g1_fixed_base_mul: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 96 + 64);
+    int rc = ctx->staging.ensure(n * 96 + 64);
     if (rc) return rc;
-    char* st = (char*)ctx->staging; // scalars | results
+    char* st = (char*)ctx->staging.p; // scalars | results
     if (n) BBG_HIP(hipMemcpyAsync(st, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = fixed_base_mul(ctx, base_affine, st, n, st + n * 32, ctx->stream); // validates the base for n = 0 as well
     if (rc || n == 0) return rc;
@@ -1176,9 +1102,9 @@ int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t ns = one_scalar ? 1 : n;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 64 + ns * 32);
+    int rc = ctx->staging.ensure(n * 64 + ns * 32);
     if (rc) return rc;
-    char* st = (char*)ctx->staging; // points (multiplied in place) | scalars
+    char* st = (char*)ctx->staging.p; // points (multiplied in place) | scalars
     BBG_HIP(hipMemcpyAsync(st, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
     BBG_HIP(hipMemcpyAsync(st + n * 64, scalars, ns * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = var_base_mul(ctx, st, st + n * 64, n, one_scalar, st, ctx->stream);
@@ -1218,12 +1144,12 @@ int bbg_ntt(bbg_ctx* ctx, uint64_t* coeffs, unsigned log2n, int op, size_t gener
     if (log2n > 28) { set_error("bbg_ntt: log2n > 28 exceeds the 2-adicity of BN254 Fr (fr.hpp:27-30)"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t bytes = ((size_t)1 << log2n) * 32;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, bytes);
+    int rc = ctx->staging.ensure(bytes);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging, coeffs, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ntt_run(ctx, ctx->staging, log2n, op, generator_size, constant, ctx->stream);
+    BBG_HIP(hipMemcpyAsync(ctx->staging.p, coeffs, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = ntt_run(ctx, ctx->staging.p, log2n, op, generator_size, constant, ctx->stream);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(coeffs, ctx->staging, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(coeffs, ctx->staging.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
@@ -1296,12 +1222,12 @@ int bbg_coset_fft_extend(bbg_ctx* ctx, const uint64_t* coeffs, unsigned log2n, u
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << log2n, m = (size_t)1 << log2_domain;
     // n coefficients land behind the m-element result area; the transform reads them zero-extended and writes the result area
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, (m + n) * 32);
+    int rc = ctx->staging.ensure((m + n) * 32);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync((char*)ctx->staging + m * 32, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = ntt_coset_extend(ctx, (char*)ctx->staging + m * 32, n, ctx->staging, log2_domain, ctx->stream);
+    BBG_HIP(hipMemcpyAsync((char*)ctx->staging.p + m * 32, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = ntt_coset_extend(ctx, (char*)ctx->staging.p + m * 32, n, ctx->staging.p, log2_domain, ctx->stream);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out, ctx->staging, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(out, ctx->staging.p, m * 32, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     memcpy(out + m * 4, out, 4 * 32); // add_lagrange_base_coefficient(out[0..3])
     return BBG_OK;
@@ -1314,12 +1240,12 @@ int bbg_coset_fft_split(bbg_ctx* ctx, uint64_t* coeffs, unsigned log2n, size_t e
     if (ext == 0 || log2n > 28 || ext > ((size_t)1 << 28)) { set_error("bbg_coset_fft_split: bad size"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << log2n;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * ext * 32);
+    int rc = ctx->staging.ensure(n * ext * 32);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = ntt_coset_split(ctx, ctx->staging, log2n, ext, ctx->stream);
+    BBG_HIP(hipMemcpyAsync(ctx->staging.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = ntt_coset_split(ctx, ctx->staging.p, log2n, ext, ctx->stream);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(coeffs, ctx->staging, n * ext * 32, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(coeffs, ctx->staging.p, n * ext * 32, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
@@ -1349,19 +1275,19 @@ int bbg_poly_evaluate(bbg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint
     CHECK_CTX(ctx);
     if ((!coeffs && n) || !z || !out) { set_error("bbg_poly_evaluate: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 32 + 32);
+    int rc = ctx->staging.ensure(n * 32 + 32);
     if (rc) return rc;
-    if (n) BBG_HIP(hipMemcpyAsync(ctx->staging, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    return poly_evaluate(ctx, ctx->staging, n, z, out, ctx->stream);
+    if (n) BBG_HIP(hipMemcpyAsync(ctx->staging.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    return poly_evaluate(ctx, ctx->staging.p, n, z, out, ctx->stream);
 }
 int bbg_kate_opening(bbg_ctx* ctx, const uint64_t* src, uint64_t* dest, size_t n, const uint64_t z[4], uint64_t f_out[4])
 {
     CHECK_CTX(ctx);
     if ((n && (!src || !dest)) || !z || !f_out) { set_error("bbg_kate_opening: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, 2 * n * 32 + 64);
+    int rc = ctx->staging.ensure(2 * n * 32 + 64);
     if (rc) return rc;
-    char* d_src = (char*)ctx->staging;
+    char* d_src = (char*)ctx->staging.p;
     char* d_dest = d_src + n * 32 + 32;
     if (n) BBG_HIP(hipMemcpyAsync(d_src, src, n * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = poly_kate_opening(ctx, d_src, d_dest, n, z, f_out, ctx->stream);
@@ -1389,10 +1315,10 @@ int bbg_poly_evaluate_lagrange(bbg_ctx* ctx, const uint64_t* evals, unsigned log
     if (!evals || !z || !out || log2n == 0 || log2n > 28) { set_error("bbg_poly_evaluate_lagrange: bad argument (1 <= log2n <= 28)"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t bytes = ((size_t)1 << log2n) * 32;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, bytes);
+    int rc = ctx->staging.ensure(bytes);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
-    const void* d_evals = ctx->staging;
+    BBG_HIP(hipMemcpyAsync(ctx->staging.p, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const void* d_evals = ctx->staging.p;
     return poly_evaluate_lagrange(ctx, &d_evals, nullptr, 1, log2n, z, out, ctx->stream);
 }
 int bbg_kate_opening_lagrange_device(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t z[4], uint64_t f_out[4])
@@ -1408,12 +1334,12 @@ int bbg_divide_by_pseudo_vanishing(bbg_ctx* ctx, uint64_t* evals, unsigned log2_
     if (log2_target > 28) { set_error("bbg_divide_by_pseudo_vanishing: log2_target > 28"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t bytes = ((size_t)1 << log2_target) * 32;
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, bytes);
+    int rc = ctx->staging.ensure(bytes);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = poly_divide_pseudo_vanishing(ctx, ctx->staging, log2_src, log2_target, num_roots_cut, ctx->stream);
+    BBG_HIP(hipMemcpyAsync(ctx->staging.p, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = poly_divide_pseudo_vanishing(ctx, ctx->staging.p, log2_src, log2_target, num_roots_cut, ctx->stream);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(evals, ctx->staging, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(evals, ctx->staging.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
@@ -1430,9 +1356,9 @@ int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint6
     if (!a || !out) { set_error("bbg_field_op: null argument"); return BBG_E_INVALID; }
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ensure_buffer(&ctx->staging, &ctx->staging_bytes, n * 96);
+    int rc = ctx->staging.ensure(n * 96);
     if (rc) return rc;
-    char* st = (char*)ctx->staging;
+    char* st = (char*)ctx->staging.p;
     BBG_HIP(hipMemcpyAsync(st, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
     if (b) BBG_HIP(hipMemcpyAsync(st + n * 32, b, n * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = field_op_device(which, op, st, b ? st + n * 32 : nullptr, st + n * 64, n, ctx->stream);

@@ -63,14 +63,38 @@ struct Srs {
     std::mutex mu;
 };
 
-struct MsmScratch {
-    void* buf = nullptr;
+// A grow-only device buffer: the one owner type of a context's (and a bbg_multi's) working memory.  No destructor frees it: its owner
+// is torn down explicitly (bbg_destroy, bbg_memory_trim) after hipSetDevice.
+struct DevBuf {
+    void* p = nullptr;
     size_t bytes = 0;
+    // at least `need` bytes; growing waits for the device (queued work may still read the old block) and does NOT keep the contents
+    int ensure(size_t need)
+    {
+        if (bytes >= need && p) return BBG_OK;
+        if (p) {
+            BBG_HIP(hipDeviceSynchronize());
+            void* old = p;
+            p = nullptr;
+            bytes = 0;
+            BBG_HIP(hipFree(old));
+        }
+        hipError_t e = hipMalloc(&p, need);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return hip_fail(e, "hipMalloc(DevBuf)", __FILE__, __LINE__);
+        }
+        bytes = need;
+        return BBG_OK;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
 };
 
-} // namespace bbg
-
-namespace bbg {
 // Optional per-kernel timing with HIP events on the launch stream (bbg_profile_*): bench.py reads the average
 // duration of the dominant kernels live from here, so the roofline numbers do not depend on an external profiler.
 struct ProfEntry {
@@ -86,15 +110,14 @@ struct bbg_ctx {
     bool own_stream = false;
     std::mutex mu;
     std::map<unsigned, bbg::NttDomain> domains;
-    void* ntt_scratch = nullptr;
-    size_t ntt_scratch_bytes = 0;
-    void* staging = nullptr; // device staging for host-pointer entry points
-    size_t staging_bytes = 0;
-    bbg::MsmScratch msm;
-    bbg::MsmScratch msm_tiny; // digit bytes, sign words and per-block bucket sums of the small-circuit MSM path (msm_tiny.hip)
+    // Working memory, grown on demand.  Every buffer but the two MSM arenas (reported as msm_arena) is listed in BBG_CTX_SCRATCH below,
+    // which is what bbg_destroy, bbg_memory_trim and bbg_memory_report walk.
+    bbg::DevBuf ntt_scratch;
+    bbg::DevBuf staging; // device staging for host-pointer entry points
+    bbg::DevBuf msm;
+    bbg::DevBuf msm_tiny; // digit bytes, sign words and per-block bucket sums of the small-circuit MSM path (msm_tiny.hip)
     uint64_t msm_tiny_layout = 0; // (n_pad, sets, slices) the buffer was last laid out for: another shape moves the double-buffered bucket sums
-    void* poly_scratch = nullptr; // evaluate / kate partial sums, pow tables
-    size_t poly_scratch_bytes = 0;
+    bbg::DevBuf poly_scratch; // evaluate / kate partial sums, pow tables
     // MSM reduce phase may run on an auxiliary stream so that it overlaps the next MSM's sort / accumulation
     // MSM_SLOTS reduce phases may be in flight at once, each on its own auxiliary stream with its own working set, so the reduce
     // phases of consecutive MSMs (latency chains that use a sliver of the chip) overlap each other as well as the next accumulation.
@@ -118,28 +141,26 @@ struct bbg_ctx {
     int msm_zero_c = 0;           // ... for this window width ...
     int msm_zero_sets = 0;        // ... and this many bucket sets (msm_layout's cap_sets)
     int msm_layout_sort = 1; // (the sort path is part of the layout: the library-sort path reserves rocPRIM's temporary storage)
-    bool msm_async_reduce = false;
+    int msm_async_reduce = 0; // option "msm_async_reduce": the reduce phase runs on an auxiliary stream (see above)
     int msm_reduce_quad = 14;   // reduce stages with four lanes per EC operation (curve_quad.hip.h): bit 0 combine (a THROUGHPUT kernel over all buckets: one lane per operation is cheaper, measured), 1 row/col, 2 planes, 3 sum
     int msm_acc_waves = 0;           // option "msm_acc_waves": lane segments per SIMD lane of the accumulation (0 = automatic), A/B
-    bool msm_limbs29 = true;         // option "msm_limbs29": the accumulation's field arithmetic on 9 x 29-bit limbs (0 = 8 x 32, A/B)
-    bool msm_accumulate_quad = true; // option "msm_accumulate_quad": small MSMs accumulate with four threads per lane segment (0 = one, A/B)
-    bool msm_reduce_low_priority = true; // auxiliary stream created with the lowest priority (option "msm_reduce_priority" = 0 undoes it)
+    int msm_limbs29 = 1;            // option "msm_limbs29": the accumulation's field arithmetic on 9 x 29-bit limbs (0 = 8 x 32, A/B)
+    int msm_accumulate_quad = 1;    // option "msm_accumulate_quad": small MSMs accumulate with four threads per lane segment (0 = one, A/B)
+    int msm_reduce_low_priority = 1; // auxiliary stream created with the lowest priority (option "msm_reduce_priority" = 0 undoes it)
     std::map<uint32_t, void*> dpv_consts; // poly.hip: Z*_H division constants per (src, target, roots cut)
     std::map<uint32_t, void*> dpv_tables; // poly.hip: the Z*_H divisor per target-domain point, same key (poly_dpv_table; the prover's round 4)
-    void* gp_totals = nullptr;  // quotient.hip: grand-product thread totals
-    size_t gp_totals_bytes = 0;
-    void* quot_setup = nullptr; // quotient.hip: derived challenges / constants
-    size_t quot_setup_bytes = 0;
+    bbg::DevBuf gp_totals;  // quotient.hip: grand-product thread totals
+    bbg::DevBuf quot_setup; // quotient.hip: derived challenges / constants
     int quotient_setup_plan = 1;     // option "quotient_setup_plan": the widgets' set-up blocks by the lanes of one wave side by side (quotient.hip k_quotient_setup_plan); 0 = the one-lane chain (A/B)
     int poly_limbs29 = 1;            // option "poly_limbs29": linear combinations and evaluations of coefficient arrays on 9 x 29-bit limbs, four terms per reduction (poly29.hip.h); 0 = the 32-bit kernels (A/B)
     int prover_fused_divide = 1;     // option "prover_fused_divide": round 4 divides by Z*_H inside the coset iFFT's first load (poly_dpv_table + ntt_coset_ifft_scaled) instead of a pass of its own; 0 = the separate pass (A/B)
     int prover_tail_window = 0;      // option "prover_tail_window" (A/B): window width of the commitments whose reduce phase ends a round (rounds 4 and 6: the host waits for them with the chip idle) -- fewer buckets, shorter tail, more windows; 0 = the automatic width
-    bool prover_ntt_batch = true;    // option "prover_ntt_batch": the wires' iFFTs (round 1) and 4n coset forms of circuits up to 2^17 gates go through ONE launch set each (grid.y = wires) instead of one per wire (A/B)
+    int prover_ntt_batch = 1;       // option "prover_ntt_batch": the wires' iFFTs (round 1) and 4n coset forms of circuits up to 2^17 gates go through ONE launch set each (grid.y = wires) instead of one per wire (A/B)
     int prover_fail_round = 0;       // option "prover_fail_round" (tests only): the next bbg_prover_round<k> returns BBG_E_HIP once -- how the shim's fallback to the reference body is exercised
     int prover_early_cosets = -1; // -1 = from 2^18 gates (default), 0 = never, 1 = always. option "prover_early_cosets": the wires' 4n coset forms are queued behind round 1's last commitment (beside its reduce phase) instead of in front of round 3's grand product
     int prover_msm_batch = 4; // option "prover_msm_batch": commitments of a prover round per launch set (0 / 1 = one each; prover.hip commit())
-    bool quotient_limbs29 = true; // option "quotient_limbs29": permutation / fixed-base / fused arithmetic + range + logic widgets on lazily reduced 29-bit limbs (quotient29.hip.h; 0 = the 32-bit kernels, A/B)
-    bool quotient_fuse = true; // option "quotient_fuse": arithmetic + range + logic widgets of a chain in one pass over the wires (0 = one kernel each, A/B)
+    int quotient_limbs29 = 1; // option "quotient_limbs29": permutation / fixed-base / fused arithmetic + range + logic widgets on lazily reduced 29-bit limbs (quotient29.hip.h; 0 = the 32-bit kernels, A/B)
+    int quotient_fuse = 1; // option "quotient_fuse": arithmetic + range + logic widgets of a chain in one pass over the wires (0 = one kernel each, A/B)
     int msm_window = 0; // 0 = automatic (msm_auto_window), or one of the compiled widths (BBG_MSM_WIDTHS)
     int msm_sort = 1; // 1 = fused recode + MSD partition sort (msm.hip), 0 = k_recode + rocPRIM radix sort + k_offsets
     int ntt_tile_log = 10; // log2(elements per LDS tile); 10/7 measured best on MI355X (profiles/r01_ntt_plan_sweep.txt)
@@ -153,20 +174,23 @@ struct bbg_ctx {
     bool ntt_attr8s_set = false;
     bool ntt_attr8_set = false, ntt_attr_set = false; // dynamic-LDS attributes of the pass kernels set on this context's device
     // fixed_base.hip: the table T[w][d-1] = d 2^(8w) B of the base point last used (one slot: another base rebuilds it in place)
-    void* fb_table = nullptr;
-    size_t fb_table_bytes = 0;
+    bbg::DevBuf fb_table;
     uint64_t fb_table_key[8] = {}; // the base's canonical bytes
     bool fb_table_valid = false;
     // var_base.hip: the lanes' tables of odd multiples (1 KiB per lane) of the windowed GLV multiplication, shared by bbg_g1_batch_mul and
     // the Lagrange transform's stages under "ecntt_mul" = 1
-    void* vb_tables = nullptr;
-    size_t vb_tables_bytes = 0;
+    bbg::DevBuf vb_tables;
     // bbg_g1_ntt*: the XYZZ working set of the transform (128 B per point), grown on demand
-    void* ecntt_work = nullptr;
-    size_t ecntt_work_bytes = 0;
+    bbg::DevBuf ecntt_work;
     int batch_mul_glv = 1;           // option "batch_mul_glv": 1 = windowed GLV (xyzz_mul_glv), 0 = the bit-serial double-and-add (xyzz_mul_fr), A/B
     long batch_mul_lanes = 1L << 17; // option "batch_mul_lanes": lanes of the variable-base kernels = tables held (a multiple of 64; 2^17 = two waves per SIMD)
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
+};
+
+// every context buffer that bbg_memory_report counts under `scratch`: a new buffer is one member above plus one entry here
+constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
+    &bbg_ctx::ntt_scratch, &bbg_ctx::staging,  &bbg_ctx::poly_scratch, &bbg_ctx::gp_totals,  &bbg_ctx::quot_setup,
+    &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,
 };
 
 // bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle
@@ -208,7 +232,7 @@ struct ProfScope {
         if (stop) (void)hipEventRecord(stop, st);
     }
 };
-int ensure_buffer(void** buf, size_t* have, size_t need);
+void msm_release_aux_streams(bbg_ctx* ctx); // bbg_capi.hip: destroys the reduce streams and their events, all handles null afterwards
 int ntt_run(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, int op, size_t generator_size, const uint64_t* constant,
             hipStream_t stream);
 int ntt_ifft_to(bbg_ctx* ctx, const void* d_in, void* d_out, unsigned log2n, hipStream_t stream);

@@ -239,22 +239,20 @@ int fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scal
     int rc = fb_canonical_base(base_affine, key);
     if (rc) return rc;
     if (n == 0) return BBG_OK;
-    if (!ctx->fb_table) {
-        BBG_HIP(hipMalloc(&ctx->fb_table, FB_TABLE_BYTES));
-        ctx->fb_table_bytes = FB_TABLE_BYTES;
-        ctx->fb_table_valid = false;
-    }
+    if (!ctx->fb_table.p) ctx->fb_table_valid = false;
+    rc = ctx->fb_table.ensure(FB_TABLE_BYTES);
+    if (rc) return rc;
     if (!ctx->fb_table_valid || memcmp(ctx->fb_table_key, key, 64) != 0) {
         ProfScope ps(ctx, "fixed_base_table", st);
         FbAffArg b;
         memcpy(b.v, key, 64);
-        hipLaunchKernelGGL(k_fb_table, dim3(FB_WINDOWS), dim3(256), 0, st, (Affine*)ctx->fb_table, b);
+        hipLaunchKernelGGL(k_fb_table, dim3(FB_WINDOWS), dim3(256), 0, st, (Affine*)ctx->fb_table.p, b);
         memcpy(ctx->fb_table_key, key, 64);
         ctx->fb_table_valid = true;
     }
     {
         ProfScope ps(ctx, "fixed_base_mul", st);
-        hipLaunchKernelGGL(k_fb_mul, dim3(grid_for((n + FB_CH - 1) / FB_CH, 64)), dim3(64), 0, st, (const Affine*)ctx->fb_table, (const Fr*)d_scalars, n,
+        hipLaunchKernelGGL(k_fb_mul, dim3(grid_for((n + FB_CH - 1) / FB_CH, 64)), dim3(64), 0, st, (const Affine*)ctx->fb_table.p, (const Fr*)d_scalars, n,
                            (Affine*)d_out);
     }
     BBG_HIP(hipGetLastError());

@@ -1291,7 +1291,7 @@ template <int C> static int msm_layout(size_t total_n, int sets, int cap_sets, b
     return BBG_OK;
 }
 
-static inline char* base_of(bbg_ctx* ctx) { return (char*)ctx->msm.buf; }
+static inline char* base_of(bbg_ctx* ctx) { return (char*)ctx->msm.p; }
 // the auxiliary streams the reduce phases run on (one per reduce slot) and their events; created with the context's first MSM
 static inline int msm_ensure_aux_streams(bbg_ctx* ctx)
 {
@@ -1300,10 +1300,15 @@ static inline int msm_ensure_aux_streams(bbg_ctx* ctx)
     // the caller queues next on the main stream (the following MSM's sort / accumulation, an NTT) is dispatched first
     int least = 0, greatest = 0;
     BBG_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
-        BBG_HIP(hipStreamCreateWithPriority(&ctx->aux_streams[k], hipStreamNonBlocking, ctx->msm_reduce_low_priority ? least : (least + greatest) / 2));
-        BBG_HIP(hipEventCreateWithFlags(&ctx->ev_acc[k], hipEventDisableTiming));
-        BBG_HIP(hipEventCreateWithFlags(&ctx->ev_done[k], hipEventDisableTiming));
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < bbg_ctx::MSM_SLOTS && e == hipSuccess; k++) {
+        e = hipStreamCreateWithPriority(&ctx->aux_streams[k], hipStreamNonBlocking, ctx->msm_reduce_low_priority ? least : (least + greatest) / 2);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_acc[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_done[k], hipEventDisableTiming);
+    }
+    if (e != hipSuccess) {
+        msm_release_aux_streams(ctx); // what the slots before the failing call hold: no handle stays behind that nothing would destroy
+        return hip_fail(e, "MSM auxiliary streams", __FILE__, __LINE__);
     }
     ctx->aux_stream = ctx->aux_streams[0];
     return BBG_OK;
@@ -1345,7 +1350,7 @@ int msm_run_c(bbg_ctx* ctx, const Srs& srs, const void* table_v, int sets, const
         ~ZeroRecordGuard() { if (!done) c->msm_zero_buf = nullptr; }
     } zero_guard{ctx};
     const size_t arena_had = ctx->msm.bytes;
-    rc = ensure_buffer(&ctx->msm.buf, &ctx->msm.bytes, L.total);
+    rc = ctx->msm.ensure(L.total);
     if (rc) return rc;
     if (ctx->msm.bytes != arena_had) ctx->msm_zero_buf = nullptr;
     rc = msm_ensure_aux_streams(ctx);
@@ -1360,18 +1365,18 @@ int msm_run_c(bbg_ctx* ctx, const Srs& srs, const void* table_v, int sets, const
         ctx->msm_layout_c = C;
         ctx->msm_layout_sort = ctx->msm_sort;
     }
-    if (ctx->msm_zero_buf != ctx->msm.buf || ctx->msm_zero_c != C || ctx->msm_zero_sets != cap_sets) {
+    if (ctx->msm_zero_buf != ctx->msm.p || ctx->msm_zero_c != C || ctx->msm_zero_sets != cap_sets) {
         // the zero-initialised regions are new (fresh arena), belong to another width, or grew: cleared once here -- then the partition
         // counters are kept clear by k_sortA_scan and the redo flags by k_redo, whatever n and batch size the following calls have
         for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++)
             if (ctx->ev_done_valid[k]) BBG_HIP(hipStreamWaitEvent(st, ctx->ev_done[k], 0));
         BBG_HIP(hipMemsetAsync(base_of(ctx), 0, L.zero_bytes, st));
-        ctx->msm_zero_buf = ctx->msm.buf;
+        ctx->msm_zero_buf = ctx->msm.p;
         ctx->msm_zero_c = C;
         ctx->msm_zero_sets = cap_sets;
     }
     const int slot = (int)(ctx->msm_seq++ % bbg_ctx::MSM_SLOTS);
-    char* base = (char*)ctx->msm.buf;
+    char* base = (char*)ctx->msm.p;
     uint32_t* keys0 = (uint32_t*)(base + L.off_keys0);
     uint32_t* vals0 = (uint32_t*)(base + L.off_vals0[slot]);
 #ifdef BBG_ROCPRIM_SORT

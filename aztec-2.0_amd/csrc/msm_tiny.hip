@@ -228,7 +228,7 @@ int msm_run_tiny(bbg_ctx* ctx, const Srs& srs, const void* table, int sets, cons
     int rc = msm_ensure_aux_streams(ctx);
     if (rc) return rc;
     // (a growing buffer is released with hipFree, which waits for whatever still reads it)
-    rc = ensure_buffer(&ctx->msm_tiny.buf, &ctx->msm_tiny.bytes, mags_bytes + signs_bytes + bbg_ctx::MSM_SLOTS * parts_bytes);
+    rc = ctx->msm_tiny.ensure(mags_bytes + signs_bytes + bbg_ctx::MSM_SLOTS * parts_bytes);
     if (rc) return rc;
     // The last kernel -- one block per MSM: the chip is idle beside it -- runs on this call's reduce stream like the bucket pipeline's reduce
     // phase (msm_async_reduce; bbg_join / msm_join wait for it), so that the NEXT MSM's recode and bucket kernels run beside it; the
@@ -244,7 +244,7 @@ int msm_run_tiny(bbg_ctx* ctx, const Srs& srs, const void* table, int sets, cons
         ctx->msm_tiny_layout = layout;
     }
     if (ctx->ev_done_valid[slot]) BBG_HIP(hipStreamWaitEvent(st, ctx->ev_done[slot], 0)); // this slot's bucket sums were last read two MSMs ago
-    uint8_t* mags = (uint8_t*)ctx->msm_tiny.buf;
+    uint8_t* mags = (uint8_t*)ctx->msm_tiny.p;
     uint32_t* signs = (uint32_t*)(mags + mags_bytes);
     Xyzz* parts = (Xyzz*)(mags + mags_bytes + signs_bytes + (size_t)slot * parts_bytes);
     if (h_scalars) BBG_HIP(hipMemcpyAsync((void*)d_scalars[0], h_scalars, n[0] * 32, hipMemcpyHostToDevice, st)); // bbg_msm: a batch of one

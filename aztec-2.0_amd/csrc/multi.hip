@@ -51,8 +51,7 @@ struct bbg_multi {
     std::vector<size_t> shard_from, shard_n;
     size_t srs_n = 0;
     // per context scratch
-    std::vector<void*> d_scal;   // MSM: this context's slice of the scalars
-    std::vector<size_t> d_scal_bytes;
+    std::vector<DevBuf> d_scal;  // MSM: this context's slice of the scalars
     std::vector<void*> d_part;   // MSM: 96-byte partial
     std::vector<void*> d_x, d_recv, d_out; // NTT: shard, received chunks, cross-DFT output
     std::vector<size_t> ntt_bytes;
@@ -374,8 +373,7 @@ int bbg_multi_create(const int* devices, int count, bbg_multi** out)
     m->srs.assign(G, nullptr);
     m->shard_from.assign(G, 0);
     m->shard_n.assign(G, 0);
-    m->d_scal.assign(G, nullptr);
-    m->d_scal_bytes.assign(G, 0);
+    m->d_scal.assign(G, DevBuf{});
     m->d_part.assign(G, nullptr);
     m->d_x.assign(G, nullptr);
     m->d_recv.assign(G, nullptr);
@@ -425,7 +423,8 @@ void bbg_multi_destroy(bbg_multi* m)
         if (!c) continue;
         (void)hipSetDevice(c->device);
         (void)hipDeviceSynchronize();
-        for (void* b : { m->d_scal[(size_t)g], m->d_part[(size_t)g], m->d_x[(size_t)g], m->d_recv[(size_t)g], m->d_out[(size_t)g] })
+        m->d_scal[(size_t)g].release();
+        for (void* b : { m->d_part[(size_t)g], m->d_x[(size_t)g], m->d_recv[(size_t)g], m->d_out[(size_t)g] })
             if (b) (void)hipFree(b);
         if (m->h_stage[(size_t)g]) (void)hipHostFree(m->h_stage[(size_t)g]);
         if (m->ev_sent[(size_t)g]) (void)hipEventDestroy(m->ev_sent[(size_t)g]);
@@ -497,11 +496,11 @@ int bbg_multi_msm(bbg_multi* m, const uint64_t* scalars, size_t from, size_t n, 
         std::lock_guard<std::mutex> lkc(c->mu);
         hipStream_t st = c->stream;
         if (cnt) {
-            r = ensure_buffer(&m->d_scal[(size_t)g], &m->d_scal_bytes[(size_t)g], cnt * 32);
+            r = m->d_scal[(size_t)g].ensure(cnt * 32);
             if (r) return r;
-            BBG_HIP(hipMemcpyAsync(m->d_scal[(size_t)g], scalars + (lo - from) * 4, cnt * 32, hipMemcpyHostToDevice, st));
+            BBG_HIP(hipMemcpyAsync(m->d_scal[(size_t)g].p, scalars + (lo - from) * 4, cnt * 32, hipMemcpyHostToDevice, st));
         }
-        r = msm_run(c, m->srs[(size_t)g]->s, m->d_scal[(size_t)g], cnt ? lo - sf : 0, cnt, m->d_part[(size_t)g], st); // cnt == 0 -> infinity
+        r = msm_run(c, m->srs[(size_t)g]->s, m->d_scal[(size_t)g].p, cnt ? lo - sf : 0, cnt, m->d_part[(size_t)g], st); // cnt == 0 -> infinity
         if (!r) r = msm_join(c, st);
         if (r) return r;
         if (m->use_rccl) return (int)BBG_OK; // the partial stays on the device: the all-gather below is ordered behind it on this stream

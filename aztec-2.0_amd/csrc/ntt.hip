@@ -511,16 +511,10 @@ void ntt_free_domain(NttDomain& d)
     d = NttDomain();
 }
 
-static int build_domain(bbg_ctx* ctx, unsigned log2n, NttDomain** out)
+// allocates and fills the tables of d (log2n and the plan are set); on failure d keeps what was allocated so far: the caller frees it
+static int fill_domain(bbg_ctx* ctx, NttDomain& d)
 {
-    auto it = ctx->domains.find(log2n);
-    if (it != ctx->domains.end()) {
-        *out = &it->second;
-        return BBG_OK;
-    }
-    NttDomain d;
-    d.log2n = log2n;
-    plan_passes(ctx, d);
+    const unsigned log2n = d.log2n;
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << log2n;
     BBG_HIP(hipMalloc(&d.consts, sizeof(DomainConsts)));
@@ -577,6 +571,25 @@ static int build_domain(bbg_ctx* ctx, unsigned log2n, NttDomain** out)
         BBG_HIP(hipMemcpyAsync(&root, &dc->root, sizeof(Fr), hipMemcpyDeviceToHost, st));
         BBG_HIP(hipStreamSynchronize(st));
         memcpy(d.root_host, &root, 32);
+    }
+    return BBG_OK;
+}
+
+static int build_domain(bbg_ctx* ctx, unsigned log2n, NttDomain** out)
+{
+    auto it = ctx->domains.find(log2n);
+    if (it != ctx->domains.end()) {
+        *out = &it->second;
+        return BBG_OK;
+    }
+    NttDomain d;
+    d.log2n = log2n;
+    plan_passes(ctx, d);
+    int rc = fill_domain(ctx, d);
+    if (rc) { // out of memory is a realistic end for a large domain (2^28: 40 GiB): nothing of a half-built one stays allocated
+        (void)hipStreamSynchronize(ctx->stream); // the fill kernels queued so far write the tables
+        ntt_free_domain(d);
+        return rc;
     }
     auto ins = ctx->domains.emplace(log2n, d);
     *out = &ins.first->second;
@@ -757,9 +770,9 @@ static int ntt_core(bbg_ctx* ctx, NttDomain& d, const Fr* in, Fr* out, int inver
         if (pre != nullptr || in_count != ~(size_t)0) { set_error("ntt_core: this plan does not fuse a pre-scale table or a zero-extended input (can_fuse)"); return BBG_E_INVALID; }
         return launch_pass(ctx, d, 0, inverse, in, out, post, st);
     }
-    int rc = ensure_buffer(&ctx->ntt_scratch, &ctx->ntt_scratch_bytes, n * sizeof(Fr));
+    int rc = ctx->ntt_scratch.ensure(n * sizeof(Fr));
     if (rc) return rc;
-    Fr* scratch = (Fr*)ctx->ntt_scratch;
+    Fr* scratch = (Fr*)ctx->ntt_scratch.p;
     // pass 0: in -> scratch (same positions); middle passes in place on scratch; last pass scratch -> out (transposing)
     rc = launch_pass(ctx, d, 0, inverse, in, scratch, nullptr, st, pre, pre_count, in_count);
     for (int q = 1; q < d.passes - 1 && !rc; q++) rc = launch_pass(ctx, d, q, inverse, scratch, scratch, nullptr, st);
@@ -779,10 +792,10 @@ static int ntt_core_batch(bbg_ctx* ctx, NttDomain& d, int count, const Fr* const
         if (pre != nullptr || in_count != ~(size_t)0) { set_error("ntt_core_batch: this plan does not fuse a pre-scale table or a zero-extended input (can_fuse)"); return BBG_E_INVALID; }
         return launch_pass(ctx, d, 0, inverse, nullptr, nullptr, post, st, nullptr, 0, ~(size_t)0, count, in, out);
     }
-    int rc = ensure_buffer(&ctx->ntt_scratch, &ctx->ntt_scratch_bytes, (size_t)count * n * sizeof(Fr));
+    int rc = ctx->ntt_scratch.ensure((size_t)count * n * sizeof(Fr));
     if (rc) return rc;
     Fr* scratch[4] = { nullptr, nullptr, nullptr, nullptr };
-    for (int k = 0; k < count; k++) scratch[k] = (Fr*)ctx->ntt_scratch + (size_t)k * n;
+    for (int k = 0; k < count; k++) scratch[k] = (Fr*)ctx->ntt_scratch.p + (size_t)k * n;
     rc = launch_pass(ctx, d, 0, inverse, nullptr, nullptr, nullptr, st, pre, pre_count, in_count, count, in, scratch);
     for (int q = 1; q < d.passes - 1 && !rc; q++) rc = launch_pass(ctx, d, q, inverse, nullptr, nullptr, nullptr, st, nullptr, 0, ~(size_t)0, count, scratch, scratch);
     if (!rc) rc = launch_pass(ctx, d, d.passes - 1, inverse, nullptr, nullptr, post, st, nullptr, 0, ~(size_t)0, count, scratch, out);
@@ -974,10 +987,10 @@ int ntt_coset_split(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, size_t ext, hi
         BBG_HIP(hipMemcpyAsync(gk, &dcs->pow2_tmp[0], sizeof(Fr), hipMemcpyDeviceToDevice, st));
     }
     // interleave through the scratch buffer (ntt_core is done with it by now on this stream)
-    rc = ensure_buffer(&ctx->ntt_scratch, &ctx->ntt_scratch_bytes, n * ext * sizeof(Fr));
+    rc = ctx->ntt_scratch.ensure(n * ext * sizeof(Fr));
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->ntt_scratch, a, n * ext * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_interleave, dim3(grid_for(n * ext, 256)), dim3(256), 0, st, (const Fr*)ctx->ntt_scratch, a, (int)log2n,
+    BBG_HIP(hipMemcpyAsync(ctx->ntt_scratch.p, a, n * ext * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_interleave, dim3(grid_for(n * ext, 256)), dim3(256), 0, st, (const Fr*)ctx->ntt_scratch.p, a, (int)log2n,
                        logext);
     BBG_HIP(hipGetLastError());
     return BBG_OK;

@@ -87,10 +87,10 @@ struct PolyHeader {
 static int poly_scratch(bbg_ctx* ctx, size_t partials, PolyHeader** hdr, Fr** part)
 {
     const size_t head = (sizeof(PolyHeader) + 255) / 256 * 256;
-    int rc = ensure_buffer(&ctx->poly_scratch, &ctx->poly_scratch_bytes, head + (partials + 2) * sizeof(Fr));
+    int rc = ctx->poly_scratch.ensure(head + (partials + 2) * sizeof(Fr));
     if (rc) return rc;
-    *hdr = (PolyHeader*)ctx->poly_scratch;
-    if (part) *part = (Fr*)((char*)ctx->poly_scratch + head);
+    *hdr = (PolyHeader*)ctx->poly_scratch.p;
+    if (part) *part = (Fr*)((char*)ctx->poly_scratch.p + head);
     return BBG_OK;
 }
 
@@ -538,7 +538,7 @@ int poly_kate_opening(bbg_ctx* ctx, const void* d_src, void* d_dest, size_t n, c
     if (!f_out) { set_error("bbg_kate_opening: bad argument"); return BBG_E_INVALID; }
     int rc = poly_kate_opening_async(ctx, d_src, d_dest, n, z, nullptr, st);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(f_out, &((PolyHeader*)ctx->poly_scratch)->ps[0].result, 32, hipMemcpyDeviceToHost, st));
+    BBG_HIP(hipMemcpyAsync(f_out, &((PolyHeader*)ctx->poly_scratch.p)->ps[0].result, 32, hipMemcpyDeviceToHost, st));
     BBG_HIP(hipStreamSynchronize(st));
     return BBG_OK;
 }

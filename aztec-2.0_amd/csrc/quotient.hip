@@ -738,9 +738,9 @@ int ntt_domain_consts(bbg_ctx* ctx, unsigned log2n, void** consts);
 constexpr int QUOT_SETUPS = 8;
 static int quot_setup_block(bbg_ctx* ctx, int slot, QuotientSetup** out)
 {
-    int rc = ensure_buffer(&ctx->quot_setup, &ctx->quot_setup_bytes, QUOT_SETUPS * sizeof(QuotientSetup));
+    int rc = ctx->quot_setup.ensure(QUOT_SETUPS * sizeof(QuotientSetup));
     if (rc) return rc;
-    *out = (QuotientSetup*)ctx->quot_setup + slot;
+    *out = (QuotientSetup*)ctx->quot_setup.p + slot;
     return BBG_OK;
 }
 
@@ -760,9 +760,9 @@ static int gp_fill(bbg_ctx* ctx, int width, const void* const* d_wires, const vo
     a.n = (size_t)1 << log2n;
     a.block_rows = (size_t)256 * gp_rows_per_thread(a.n);
     a.nblocks = (a.n + a.block_rows - 1) / a.block_rows;
-    int rc = ensure_buffer(&ctx->gp_totals, &ctx->gp_totals_bytes, (a.n + 2 * a.nblocks + 2) * sizeof(Fr));
+    int rc = ctx->gp_totals.ensure((a.n + 2 * a.nblocks + 2) * sizeof(Fr));
     if (rc) return rc;
-    a.sd = (Fr*)ctx->gp_totals;
+    a.sd = (Fr*)ctx->gp_totals.p;
     a.bt = a.sd + a.n;
     a.z = (Fr*)d_z;
     QuotientSetup* setup = nullptr;

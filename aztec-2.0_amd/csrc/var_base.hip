@@ -53,10 +53,10 @@ int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables)
     size_t l = (work + 63) / 64 * 64;
     if (l > (size_t)ctx->batch_mul_lanes) l = (size_t)ctx->batch_mul_lanes;
     if (l == 0) l = 64;
-    int rc = ensure_buffer(&ctx->vb_tables, &ctx->vb_tables_bytes, l * GLV_TABLE_BYTES);
+    int rc = ctx->vb_tables.ensure(l * GLV_TABLE_BYTES);
     if (rc) return rc;
     *lanes = l;
-    *tables = ctx->vb_tables;
+    *tables = ctx->vb_tables.p;
     return BBG_OK;
 }
 

@@ -513,12 +513,16 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
  * "ntt_kernel" (2 = register-resident radix-8 passes, default; 1 = radix-2 in LDS),
  * "ntt_max_logr8" (6..11, max log-radix per radix-8 pass, default 10), "ntt_big_tile" (0 / 1 / 2: 4096-element tiles for 2^21 [default] / also 2^22),
  * "ntt_lds_planes" (2 = a pass keeps its tile in LDS between two radix-8 steps, 1 = the tile moves one 16-byte plane at a time through half the LDS with
- * three waves per SIMD, 0 = automatic [default]: 1 from 2^22), "prover_msm_batch" (0 .. BBG_MSM_BATCH_MAX, default 4: commitments of a bbg_prover round per
+ * three waves per SIMD, 0 = automatic [default]: 1 from 2^22), "ntt_limbs29" (1 = the radix-8 passes compute on lazily reduced 9 x 29-bit limbs,
+ * 0 = on 8 x 32-bit limbs, -1 = automatic, default), "prover_msm_batch" (0 .. BBG_MSM_BATCH_MAX, default 4: commitments of a bbg_prover round per
  * launch set; 0 / 1 = one launch set each),
  * "batch_mul_glv" (1 = bbg_g1_batch_mul* multiplies with the windowed GLV form, default; 0 = with the bit-serial double-and-add, A/B),
  * "batch_mul_lanes" (a multiple of 64 in 64 .. 2^20, default 2^17: lanes of the variable-base kernels, each holding a 1 KiB table and walking
  * the points with that stride), "ecntt_mul" (1 = the stages of the G1 transforms -- bbg_srs_lagrange, bbg_g1_ntt, bbg_open_all -- multiply with the
  * windowed GLV form, default; 0 = bit-serially, A/B).
+ * "prover_fail_round" is a test hook, not a tuning option: the next bbg_prover_round<value> fails once as a device error would.  It is refused
+ * with BBG_E_INVALID unless the process was started with BBG_TEST_HOOKS=1.
+ * A null or unknown key and a value outside a key's range return BBG_E_INVALID and leave the context unchanged.
  * Every value of every option gives bit-identical results; they exist for A/B measurements. */
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",

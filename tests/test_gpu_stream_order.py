@@ -14,7 +14,7 @@ set before and restored after.
 
 Each unsynchronised section runs twice: a first pass into scratch buffers, then a full host synchronisation, then the pass that is checked.
 The first pass is not a retry.  It takes the first-use work out of the checked pass -- window tables, the scratch arena and its growth
-(ensure_buffer synchronises the device before it frees), NTT tables -- because a host synchronisation inside the section would hide a
+(DevBuf::ensure synchronises the device before it frees), NTT tables -- because a host synchronisation inside the section would hide a
 missing device-side wait.
 
 Expected values come from the C oracle on the same inputs (pippenger, msm_naive, g1_sum, g1_mul, ntt, poly_binop), compared bit for bit
