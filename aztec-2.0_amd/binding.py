@@ -91,6 +91,8 @@ def load_library():
         "bbg_g1_ntt": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_g1_ntt_device": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_open_all_prepare": (cint, [vp, vp, ctypes.c_uint, ctypes.POINTER(vp)]),
+        "bbg_open_all_prepare_cells": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(vp)]),
+        "bbg_open_all_count": (cint, [vp, ctypes.POINTER(sz)]),
         "bbg_open_all_device": (cint, [vp, vp, vp]),
         "bbg_open_all": (cint, [vp, vp, vp]),
         "bbg_open_all_device_bytes": (cint, [vp, ctypes.POINTER(sz)]),
@@ -180,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "bbg_fr_batch_invert_device", "bbg_poly_evaluate_lagrange_device", "bbg_poly_evaluate_lagrange", "bbg_kate_opening_lagrange_device",
     "bbg_prover_evaluate_lagrange",
     "bbg_g1_ntt", "bbg_g1_ntt_device", "bbg_open_all_prepare", "bbg_open_all_device", "bbg_open_all", "bbg_open_all_device_bytes", "bbg_open_all_free",
+    "bbg_open_all_prepare_cells", "bbg_open_all_count",
 ]
 
 
@@ -238,22 +241,31 @@ class Srs:
 
 
 class OpenAll:
-    """A prepared bbg_open_all handle: all n = 2^log2n opening proofs of a polynomial on its own domain per call."""
+    """A prepared bbg_open_all handle: all n = 2^log2n opening proofs of a polynomial on its own domain per call, or, prepared with
+    log2cell > 0, its n >> log2cell cell proofs (one per coset of 2^log2cell domain points)."""
 
     def __init__(self, owner, handle, log2n):
         self._owner, self.handle, self.log2n = owner, handle, log2n
 
+    @property
+    def count(self):
+        """The number of proofs a call writes (bbg_open_all_count)."""
+        c = ctypes.c_size_t()
+        self._owner._ck(self._owner.lib.bbg_open_all_count(self.handle, ctypes.byref(c)))
+        return int(c.value)
+
     def open(self, coeffs):
-        """(n, 8) canonical affine proofs, out[m] = commitment to (f(X) - f(w^m)) / (X - w^m), for (n, 4) Montgomery coefficients (bbg_open_all)."""
+        """(count, 8) canonical affine proofs for (n, 4) Montgomery coefficients (bbg_open_all): out[m] = commitment to
+        (f(X) - f(w^m)) / (X - w^m), or for a cell handle to the quotient of f by X^l - w^(l m)."""
         c = _u64(coeffs, 4)
         if c.shape[0] != 1 << self.log2n:
             raise ValueError(f"expected {1 << self.log2n} coefficients, got {c.shape[0]}")
-        out = np.zeros((c.shape[0], 8), dtype=np.uint64)
+        out = np.zeros((self.count, 8), dtype=np.uint64)
         self._owner._ck(self._owner.lib.bbg_open_all(self.handle, c.ctypes.data, out.ctypes.data))
         return out
 
     def open_device(self, d_coeffs, d_out):
-        """Device pointers; asynchronous on the context stream (bbg_open_all_device)."""
+        """Device pointers, d_out of count x 64 B; asynchronous on the context stream (bbg_open_all_device)."""
         self._owner._ck(self._owner.lib.bbg_open_all_device(self.handle, ctypes.c_void_p(d_coeffs), ctypes.c_void_p(d_out)))
 
     def device_bytes(self):
@@ -450,10 +462,14 @@ class Bbg:
         """Device pointers, d_out may be d_points; asynchronous (bbg_g1_ntt_device)."""
         self._ck(self.lib.bbg_g1_ntt_device(self.ctx, ctypes.c_void_p(d_points), log2n, int(bool(inverse)), ctypes.c_void_p(d_out)))
 
-    def open_all_prepare(self, srs, log2n):
-        """An OpenAll for polynomials of 2^log2n coefficients over the first 2^log2n - 1 points of srs (bbg_open_all_prepare)."""
+    def open_all_prepare(self, srs, log2n, log2cell=0):
+        """An OpenAll for polynomials of 2^log2n coefficients over the first 2^log2n - 1 points of srs (bbg_open_all_prepare); with
+        log2cell > 0 one that proves cells of 2^log2cell points (bbg_open_all_prepare_cells)."""
         h = ctypes.c_void_p()
-        self._ck(self.lib.bbg_open_all_prepare(self.ctx, srs.handle, log2n, ctypes.byref(h)))
+        if log2cell == 0:
+            self._ck(self.lib.bbg_open_all_prepare(self.ctx, srs.handle, log2n, ctypes.byref(h)))
+        else:
+            self._ck(self.lib.bbg_open_all_prepare_cells(self.ctx, srs.handle, log2n, log2cell, ctypes.byref(h)))
         return OpenAll(self, h, log2n)
 
     # ---- NTT

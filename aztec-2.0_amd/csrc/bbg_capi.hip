@@ -880,6 +880,26 @@ int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_
     return open_all_prepare(ctx, srs->s.points, log2n, out);
 }
 
+int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, struct bbg_open_all** out)
+{
+    if (log2cell == 0) return bbg_open_all_prepare(ctx, srs, log2n, out);
+    CHECK_CTX(ctx);
+    if (!srs || !out) { set_error("bbg_open_all_prepare_cells: null argument"); return BBG_E_INVALID; }
+    if (log2n < 1 || log2n > 27) { set_error("bbg_open_all_prepare_cells: log2n must be 1 .. 27"); return BBG_E_INVALID; }
+    if (log2cell > log2n - 1) { set_error("bbg_open_all_prepare_cells: log2cell must be 0 .. log2n - 1"); return BBG_E_INVALID; }
+    if (((size_t)1 << log2n) > srs->s.n) { set_error("bbg_open_all_prepare_cells: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
+    if (srs->s.device != ctx->device) { set_error("bbg_open_all_prepare_cells: the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return open_cells_prepare(ctx, srs->s.points, log2n, log2cell, out);
+}
+
+int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs)
+{
+    if (!h || !proofs) { set_error("bbg_open_all_count: null argument"); return BBG_E_INVALID; }
+    *proofs = (size_t)1 << (h->log2n - h->log2cell);
+    return BBG_OK;
+}
+
 int bbg_open_all_device(struct bbg_open_all* h, const void* d_coeffs, void* d_out_affine)
 {
     if (!h || !d_coeffs || !d_out_affine) { set_error("bbg_open_all_device: null argument"); return BBG_E_INVALID; }
@@ -894,14 +914,14 @@ int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_a
     bbg_ctx* ctx = h->ctx;
     CHECK_CTX(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t n = (size_t)1 << h->log2n;
+    const size_t n = (size_t)1 << h->log2n, proofs = n >> h->log2cell;
     int rc = ctx->staging.ensure(n * 96);
     if (rc) return rc;
     char* st = (char*)ctx->staging.p; // proofs | coefficients
     BBG_HIP(hipMemcpyAsync(st + n * 64, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
     rc = open_all_run(h, st + n * 64, st, ctx->stream);
     if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(out_affine, st, proofs * 64, hipMemcpyDeviceToHost, ctx->stream));
     BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
@@ -909,7 +929,7 @@ int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_a
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes)
 {
     if (!h || !bytes) { set_error("bbg_open_all_device_bytes: null argument"); return BBG_E_INVALID; }
-    *bytes = open_all_bytes(h->log2n);
+    *bytes = open_all_bytes(h->log2n, h->log2cell);
     return BBG_OK;
 }
 

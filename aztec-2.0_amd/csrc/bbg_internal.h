@@ -193,14 +193,17 @@ constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,
 };
 
-// bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle
+// bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle.
+// bbg_open_all_prepare_cells with l = 2^log2cell > 1, r = n / l: s_hat holds the l transforms at 2r of the string's residue classes
 struct bbg_open_all {
     bbg_ctx* ctx = nullptr;
     unsigned log2n = 0;
+    unsigned log2cell = 0;
     void* s_hat = nullptr;  // 2n x 64 B affine, infinities possible
-    void* work2 = nullptr;  // 2n x 128 B XYZZ: the inverse transform's working array
-    void* work1 = nullptr;  // n x 128 B XYZZ: the forward transform's
+    void* work2 = nullptr;  // 2n x 128 B XYZZ: the inverse transform's working array; cells: the 2n products
+    void* work1 = nullptr;  // n x 128 B XYZZ: the forward transform's; cells: r x 128 B
     void* c_hat = nullptr;  // 2n x 32 B Fr
+    void* sum = nullptr;    // cells only: 2r x 128 B XYZZ, the summed products = the inverse transform's working array
 };
 
 struct bbg_srs {
@@ -315,6 +318,8 @@ int ecntt_run(bbg_ctx* ctx, const void* d_src, unsigned log2n, int inverse, void
 // its three steps: d_work[i] = d_src[bitrev(i)] as XYZZ; the log2n stages in place on d_work (bit-reversed in, natural out); d_work -> affine
 int ecntt_load(const void* d_src, unsigned log2n, void* d_work, hipStream_t stream);
 int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t stream);
+// the forward stages of the 2^(log2n - log2block) contiguous blocks of 2^log2block points of d_work, each block a transform of its own
+int ecntt_stages_blocks(bbg_ctx* ctx, void* d_work, unsigned log2n, unsigned log2block, hipStream_t stream);
 int ecntt_normalize(bbg_ctx* ctx, const void* d_work, size_t n, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
 // fixed_base.hip: d_out[i] = d_scalars[i] * B (64 B canonical affine, aff_inf() for an infinite result) from the context's table of B's
 // multiples, which is built on first use and rebuilt for another base.  base_affine: HOST, NULL = the generator; BBG_E_INVALID when it is
@@ -330,7 +335,8 @@ int var_base_mul(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size
 int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables);
 // open_all.hip
 int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out);
+int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
 int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t stream);
-size_t open_all_bytes(unsigned log2n);
+size_t open_all_bytes(unsigned log2n, unsigned log2cell);
 void open_all_release(struct bbg_open_all* h);
 } // namespace bbg

@@ -27,7 +27,9 @@
 // bbg_g1_ntt and the two transforms inside bbg_open_all (open_all.hip), which runs the stages on XYZZ working arrays it already holds:
 //   * the stage kernels take the direction as a template parameter.  <true> is the inverse described above; <false> is the forward
 //     transform out[k] = sum_j w_n^(jk) P_j: twiddles from the table of root^(2^b), and no n^-1 in the last stage;
-//   * k_ecntt_normalize<true> stores a point at infinity as aff_inf() and raises no flag.
+//   * k_ecntt_normalize<true> stores a point at infinity as aff_inf() and raises no flag;
+//   * ecntt_stages_blocks stops the forward stages early: many independent transforms of contiguous blocks in one pass (the cell handle
+//     of open_all.hip prepares its strings that way).
 #include "bbg_internal.h"
 #include "curve.hip.h"
 #include "ecntt.hip.h" // bit_reverse
@@ -139,9 +141,9 @@ int ecntt_load(const void* d_src, unsigned log2n, void* d_work, hipStream_t st)
     return BBG_OK;
 }
 
-// The log2n stages on `st`, in place on d_work (2^log2n XYZZ points in bit-reversed order; natural order afterwards).  inverse != 0: with
-// w_n^-1 and n^-1, else with w_n and no scaling.  The lanes' tables come from the context (var_base_tables) under "ecntt_mul" = 1.
-int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t st)
+// The first `stages` of the log2n stages on `st`, in place on d_work.  The lanes' tables come from the context (var_base_tables) under
+// "ecntt_mul" = 1.
+static int ecntt_stages_upto(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, unsigned stages, hipStream_t st)
 {
     if (log2n < 1 || log2n > 28) { set_error("ecntt: log2n out of range (1 .. 28)"); return BBG_E_INVALID; }
     void* consts = nullptr;
@@ -156,7 +158,7 @@ int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStr
     }
     auto glv = inverse ? k_ecntt_stage_glv<true> : k_ecntt_stage_glv<false>;
     auto serial = inverse ? k_ecntt_stage<true> : k_ecntt_stage<false>;
-    for (unsigned s = 0; s < log2n; s++) {
+    for (unsigned s = 0; s < stages; s++) {
         const int last = s + 1 == log2n ? 1 : 0;
         if (ctx->ecntt_mul)
             hipLaunchKernelGGL(glv, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last, (Xyzz*)tables);
@@ -165,6 +167,23 @@ int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStr
     }
     BBG_HIP(hipGetLastError());
     return BBG_OK;
+}
+
+// The log2n stages on `st`, in place on d_work (2^log2n XYZZ points in bit-reversed order; natural order afterwards).  inverse != 0: with
+// w_n^-1 and n^-1, else with w_n and no scaling.
+int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t st)
+{
+    return ecntt_stages_upto(ctx, d_work, log2n, inverse, log2n, st);
+}
+
+// 2^(log2n - log2block) independent FORWARD transforms of 2^log2block points each, in place on the contiguous blocks of d_work (each
+// bit-reversed within itself): the first log2block stages of the schedule over the whole array.  Stage s takes w_2m^j, m = 2^s, whatever
+// the array length -- the stage kernels rebuild it from the 2^log2n domain's table as j << (log2n - 1 - s).  The inverse folds n^-1 into
+// its last stage and has no such form.
+int ecntt_stages_blocks(bbg_ctx* ctx, void* d_work, unsigned log2n, unsigned log2block, hipStream_t st)
+{
+    if (log2block < 1 || log2block > log2n) { set_error("ecntt: block size out of range"); return BBG_E_INVALID; }
+    return ecntt_stages_upto(ctx, d_work, log2n, 0, log2block, st);
 }
 
 // d_out[i] = d_work[i] as canonical affine on `st`, n points.  d_inf_flag != null: a point at infinity sets *d_inf_flag (cleared by the

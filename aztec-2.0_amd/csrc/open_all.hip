@@ -28,6 +28,29 @@
 //   * k_open_all_fold       the first n entries, bit-reversed, into the size-n working array, still XYZZ;
 //   * the forward stages at n;
 //   * one normalisation, which writes a proof at infinity as aff_inf() (f constant, for one).
+//
+// Cells (bbg_open_all_prepare_cells, l = 2^log2cell >= 2, r = n / l, phi = w^l): one proof per coset w^m <w^r>, m < r, the commitment to
+// q_m in f = q_m (X^l - phi^m) + I_m, deg I_m < l.  q_m has the coefficients q_j = sum_(k>=1) f_(j+kl) phi^(m(k-1)), so
+//
+//     proof_m = sum_(u=0)^(r-2) phi^(m u) h_u,      h_u = sum_(j=0)^(n-1-(u+1)l) f_(j+(u+1)l) s_j,   h_(r-1) = infinity:
+//
+// the forward G1 NTT of size r of h.  With j = l a + b, f^(b)_i = f_(l i + b) and s^(b)_a = s_(l a + b), h = sum_(b<l) h^(b) and
+// h^(b)_k = sum_(i=k+1)^(r-1) f^(b)_i s^(b)_(i-1-k) is the Toeplitz form above with n -> r, once per residue class b:
+//
+//     s^(b) = (s^(b)_(r-2), .., s^(b)_0, then r+1 infinities)          c^(b) = (f^(b)_(r-1), then r+1 zeros, then f^(b)_1, .., f^(b)_(r-2))
+//     h     = the first r entries of iNTT_G1,2r( sum_b NTT_Fr,2r(c^(b)) o NTT_G1,2r(s^(b)) )
+//
+// f_0 .. f_(l-1) are never read, the points s_0 .. s_(n-l-1) are.  tests/tools/open_cells_model.py is this on the oracle.  The handle keeps
+// s_hat[b 2r + i] = NTT_G1,2r(s^(b))[i], 2n affine points.  All l transforms are ONE pass of the stage kernels over an array of 2n: the
+// first log2(2r) stages of a decimation-in-time schedule over 2n points are l independent transforms of the contiguous blocks of 2r
+// (ecntt_stages_blocks), and because bitrev_2n(b 2r + i) = bitrev_2r(i) l + bitrev_l(b), ecntt_load over 2n leaves every block
+// bit-reversed within itself when k_open_cells_srs lays the source out as src[k l + c] = s^(bitrev_l(c))[k].  A call queues:
+//   * k_open_cells_coeffs   c_hat[b 2r + i] = c^(b)[i];
+//   * l Fr NTTs at 2r       on the contiguous blocks;
+//   * k_open_all_pointwise  over all 2n items with log2m = log2(2n): product (b, i) lands at work2[bitrev_2r(i) l + bitrev_l(b)] by the
+//                           same identity -- the l products of output index i contiguous, at the position the inverse stages want;
+//   * k_open_cells_sum      sum[k] = sum_(t<l) work2[k l + t], k < 2r, by the complete addition;
+//   * the inverse stages at 2r, k_open_all_fold at r, the forward stages at r, one normalisation of r points.
 #include "bbg_internal.h"
 #include "curve.hip.h"
 #include "ecntt.hip.h" // bit_reverse
@@ -81,11 +104,50 @@ __global__ void __launch_bounds__(256) k_open_all_fold(const Xyzz* __restrict__ 
     xyzz_store(dst + i, xyzz_load(src + bit_reverse(i, log2n)));
 }
 
-// ---------------------------------------------------------------------------------------------- host side
-size_t open_all_bytes(unsigned log2n)
+// cells: src[k l + c] = s^(b)[k] with b = bitrev_l(c), k < 2r: s_(l (r-2-k) + b) for k <= r-2, aff_inf() above.  2n entries; log2cell >= 1.
+__global__ void __launch_bounds__(256) k_open_cells_srs(const Affine* __restrict__ srs, Affine* __restrict__ src, unsigned log2n, unsigned log2cell)
 {
-    const size_t n = (size_t)1 << log2n;
-    return 2 * n * 64 + 2 * n * 128 + n * 128 + 2 * n * 32;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = (size_t)1 << log2n, r = n >> log2cell;
+    if (j >= 2 * n) return;
+    const size_t k = j >> log2cell, b = bit_reverse(j & (((size_t)1 << log2cell) - 1), log2cell);
+    aff_store(src + j, k + 2 <= r ? aff_load(srs + (((r - 2 - k) << log2cell) + b)) : aff_inf());
+}
+
+// cells: c_hat[b 2r + i] = c^(b)[i]: f_(l (r-1) + b) at i = 0, f_(l (i-r-1) + b) for i = r+2 .. 2r-1, zero elsewhere.  2n entries, the
+// words copied as they come.
+__global__ void __launch_bounds__(256) k_open_cells_coeffs(const Fr* __restrict__ f, Fr* __restrict__ c_hat, unsigned log2n, unsigned log2cell)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = (size_t)1 << log2n, r = n >> log2cell;
+    if (j >= 2 * n) return;
+    const size_t b = j >> (log2n - log2cell + 1), i = j & (2 * r - 1);
+    Fr v = Fr::zero();
+    if (i == 0) v = fe_load<FrP>(f + (((r - 1) << log2cell) + b));
+    else if (i >= r + 2) v = fe_load<FrP>(f + (((i - r - 1) << log2cell) + b));
+    fe_store<FrP>(c_hat + j, v);
+}
+
+// cells: dst[k] = sum_(t < 2^log2cell) src[k 2^log2cell + t], k < count.  One thread per output, its entries added one after the other by
+// the complete addition: designed inputs make them equal, opposite and infinite.  2n additions per call beside 2n multiplications of
+// about 200 group operations each.
+__global__ void __launch_bounds__(64) k_open_cells_sum(const Xyzz* __restrict__ src, Xyzz* __restrict__ dst, size_t count, unsigned log2cell)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const Xyzz* seg = src + (k << log2cell);
+    Xyzz acc = xyzz_load(seg);
+#pragma unroll 1
+    for (size_t t = 1; t < ((size_t)1 << log2cell); t++) acc = xyzz_add(acc, xyzz_load(seg + t));
+    xyzz_store(dst + k, acc);
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+size_t open_all_bytes(unsigned log2n, unsigned log2cell)
+{
+    const size_t n = (size_t)1 << log2n, r = n >> log2cell;
+    if (log2cell == 0) return 2 * n * 64 + 2 * n * 128 + n * 128 + 2 * n * 32;
+    return 2 * n * 64 + 2 * n * 128 + 2 * n * 32 + 2 * r * 128 + r * 128;
 }
 
 void open_all_release(struct bbg_open_all* h)
@@ -93,6 +155,7 @@ void open_all_release(struct bbg_open_all* h)
     if (h->s_hat) (void)hipFree(h->s_hat);
     if (h->work2) (void)hipFree(h->work2);
     if (h->work1) (void)hipFree(h->work1);
+    if (h->sum) (void)hipFree(h->sum);
     if (h->c_hat) (void)hipFree(h->c_hat);
     delete h;
 }
@@ -129,9 +192,95 @@ int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, str
     return BBG_OK;
 }
 
-// d_coeffs: 2^log2n Montgomery Fr (read only); d_out: 2^log2n x 64 B.  Queues only.
+// The cell handle, 1 <= log2cell <= log2n - 1.  d_srs_points: at least 2^log2n - 2^log2cell plain affine points on the context's device,
+// read once.  Synchronises the stream before it returns.
+int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out)
+{
+    const size_t n = (size_t)1 << log2n, r = n >> log2cell;
+    const unsigned log2r = log2n - log2cell;
+    hipStream_t st = ctx->stream;
+    struct bbg_open_all* h = new struct bbg_open_all;
+    h->ctx = ctx;
+    h->log2n = log2n;
+    h->log2cell = log2cell;
+    int rc = BBG_OK;
+    hipError_t e = hipMalloc(&h->s_hat, 2 * n * 64);
+    if (e == hipSuccess) e = hipMalloc(&h->work2, 2 * n * 128);
+    if (e == hipSuccess) e = hipMalloc(&h->c_hat, 2 * n * 32);
+    if (e == hipSuccess) e = hipMalloc(&h->sum, 2 * r * 128);
+    if (e == hipSuccess) e = hipMalloc(&h->work1, r * 128);
+    if (e != hipSuccess) rc = hip_fail(e, "bbg_open_all_prepare_cells: the handle's buffers", __FILE__, __LINE__);
+    if (rc == BBG_OK) {
+        ProfScope ps(ctx, "open_all_prepare", st);
+        hipLaunchKernelGGL(k_open_cells_srs, dim3(grid_for(2 * n, 256)), dim3(256), 0, st, (const Affine*)d_srs_points, (Affine*)h->s_hat, log2n, log2cell);
+        rc = ecntt_load(h->s_hat, log2n + 1, h->work2, st); // every block of 2r bit-reversed within itself
+        if (rc == BBG_OK) rc = ecntt_stages_blocks(ctx, h->work2, log2n + 1, log2r + 1, st);
+        if (rc == BBG_OK) rc = ecntt_normalize(ctx, h->work2, 2 * n, h->s_hat, nullptr, st); // infinite outputs are kept as such
+    }
+    if (rc == BBG_OK) {
+        e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = hip_fail(e, "bbg_open_all_prepare_cells", __FILE__, __LINE__);
+    }
+    if (rc) {
+        open_all_release(h);
+        return rc;
+    }
+    *out = h;
+    return BBG_OK;
+}
+
+// d_coeffs: 2^log2n Montgomery Fr (read only); d_out: 2^(log2n - log2cell) x 64 B.  Queues only.
+static int open_cells_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t st)
+{
+    bbg_ctx* ctx = h->ctx;
+    const unsigned log2n = h->log2n, log2cell = h->log2cell, log2r = log2n - log2cell, log2m = log2n + 1;
+    const size_t n = (size_t)1 << log2n, m = 2 * n, r = n >> log2cell;
+    // the largest table set of the call first, as in open_all_run
+    size_t lanes = 0;
+    void* tables = nullptr;
+    int rc = var_base_tables(ctx, m, &lanes, &tables);
+    if (rc) return rc;
+    {
+        ProfScope ps(ctx, "open_all_coeffs", st);
+        hipLaunchKernelGGL(k_open_cells_coeffs, dim3(grid_for(m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, (Fr*)h->c_hat, log2n, log2cell);
+    }
+    for (size_t b = 0; b < ((size_t)1 << log2cell); b++) {
+        rc = ntt_run(ctx, (Fr*)h->c_hat + b * 2 * r, log2r + 1, BBG_FFT, 0, nullptr, st);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(ctx, "open_all_pointwise", st);
+        hipLaunchKernelGGL(k_open_all_pointwise, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (const Affine*)h->s_hat, (const Fr*)h->c_hat, (Xyzz*)h->work2, log2m,
+                           (Xyzz*)tables);
+    }
+    {
+        ProfScope ps(ctx, "open_cells_sum", st);
+        hipLaunchKernelGGL(k_open_cells_sum, dim3(grid_for(2 * r, 64)), dim3(64), 0, st, (const Xyzz*)h->work2, (Xyzz*)h->sum, 2 * r, log2cell);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        rc = ecntt_stages(ctx, h->sum, log2r + 1, 1, st);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(ctx, "open_all_fold", st);
+        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(r, 256)), dim3(256), 0, st, (const Xyzz*)h->sum, (Xyzz*)h->work1, log2r);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        rc = ecntt_stages(ctx, h->work1, log2r, 0, st);
+        if (rc) return rc;
+    }
+    rc = ecntt_normalize(ctx, h->work1, r, d_out, nullptr, st);
+    if (rc) return rc;
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+// d_coeffs: 2^log2n Montgomery Fr (read only); d_out: 2^(log2n - log2cell) x 64 B.  Queues only.
 int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t st)
 {
+    if (h->log2cell) return open_cells_run(h, d_coeffs, d_out, st);
     bbg_ctx* ctx = h->ctx;
     const unsigned log2n = h->log2n, log2m = log2n + 1;
     const size_t n = (size_t)1 << log2n, m = 2 * n;

@@ -204,10 +204,28 @@ struct bbg_open_all; /* the handle; no typedef, because bbg_open_all is also the
  * bbg_memory_trim does not touch.  Null pointers, log2n outside 1 .. 27 and n above the SRS length are BBG_E_INVALID.  The SRS is NOT
  * required to be a powers string: the definition above holds for any points. */
 int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_open_all** out);
+/* Cells: one proof per coset of l = 2^log2cell domain points instead of one per point (the multi-proof half of Feist-Khovratovich; the
+ * unit data-availability sampling opens).  With r = n / l and phi = w_n^l, cell m (m < r) is the coset w_n^m <w_n^r> = { w_n^(m + r t) :
+ * t < l }, whose vanishing polynomial is X^l - phi^m, and with f = q_m (X^l - phi^m) + I_m, deg I_m < l,
+ *     out[m] = commitment over the s_j to q_m = sum_(u=0)^(r-2) phi^(m u) h_u,   h_u = sum_(j=0)^(n-1-(u+1)l) f_(j+(u+1)l) s_j,
+ * r proofs in natural order of m.  Over a powers string s_j = [x^j] G that is [(f(x) - I_m(x)) / (x^l - phi^m)] G.  The checks are those
+ * of bbg_open_all_prepare, plus log2cell <= log2n - 1 (at least two cells); a violation is BBG_E_INVALID and leaves *out as it was.
+ * log2cell = 0 IS bbg_open_all_prepare.  For log2cell >= 1 the points s_0 .. s_(n-l-1) are read, once, and the call synchronises: `srs`
+ * may be freed at once.  The handle holds l G1 transforms at 2r of the string's residue classes, and a call then runs G1 transforms at 2r
+ * and r instead of 2n and n.  Its memory: 2n x 64 B of transformed points, 2n x 128 B of products, 2n x 32 B of scalars, 2r x 128 B +
+ * r x 128 B of working arrays (bbg_open_all_device_bytes), outside bbg_memory_report like the all-points handle's.
+ *   The VALUES of cell m are f(w_n^(m + r t)), t < l: bbg_ntt(BBG_FFT) of the n coefficients, read at index m with stride r.  This
+ * library does not compute them here and does not verify: checking a cell proof pairs against [x^l]_2, a G2 point that this library
+ * does not make. */
+int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
+/* The number of proofs a call writes: n >> log2cell (n for a handle of bbg_open_all_prepare). */
+int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs);
 /* d_coeffs: n Montgomery Fr coefficients on the device (any representative in [0, 2r)), read only; f_0 is never read.  d_out_affine:
  * n x 64 B canonical Montgomery affine; a proof at infinity (every one of a constant f) is written as bbg_g1_ntt writes it.  Asynchronous
  * on the context stream, no host synchronisation; calls through one handle are ordered by that stream and share its working arrays.
- * Timed under "open_all_coeffs", "ntt_pass", "open_all_pointwise", "ecntt_stages", "open_all_fold", "ecntt_normalize". */
+ * Timed under "open_all_coeffs", "ntt_pass", "open_all_pointwise", "ecntt_stages", "open_all_fold", "ecntt_normalize".
+ * A cell handle writes bbg_open_all_count proofs, (n >> log2cell) x 64 B, never reads f_0 .. f_(l-1) (every proof of a polynomial of
+ * degree below l is the point at infinity), and is also timed under "open_cells_sum". */
 int bbg_open_all_device(struct bbg_open_all* h, const void* d_coeffs, void* d_out_affine);
 /* Host arrays; returns when the proofs are in out_affine. */
 int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_affine);
@@ -527,7 +545,7 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
  * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul",
- * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold".  enable(…, 1) clears previous samples. */
+ * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
