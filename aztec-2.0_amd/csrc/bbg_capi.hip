@@ -360,7 +360,7 @@ int bbg_memory_report(bbg_ctx* ctx, bbg_memory_info* out)
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
     for (const auto& kv : ctx->domains) {
-        out->ntt_tables += kv.second.bytes;
+        out->ntt_tables += kv.second.bytes();
         out->ntt_domains++;
     }
     for (const auto& kv : ctx->dpv_tables) out->ntt_tables += (size_t)32 << ((kv.first >> 8) & 0xff); // poly_dpv_table: one Fr per target-domain point

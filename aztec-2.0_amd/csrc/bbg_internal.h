@@ -26,43 +26,6 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // blocks of `block` threads that cover n items
 static inline int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
-// ---------------------------------------------------------------------------------------------- NTT
-constexpr int NTT_MAX_PASSES = 4;
-
-// Per-domain-size device tables: the GPU counterpart of evaluation_domain::compute_lookup_table()
-// (reference polynomials/evaluation_domain.cpp:33-55,169-175).  Built once per log2(n), cached in the context.
-struct NttDomain {
-    unsigned log2n = 0;
-    int passes = 0;
-    bool use_pass8 = false; // register-resident radix-8 pass kernel (ntt_pass8.hip.h) vs the radix-2-in-LDS one
-    int tile_log8 = 11;     // its tile: 2^11 elements (256 threads) or 2^12 (512 threads: 2^21 / 2^22 in two passes)
-    bool inv_scaled = false; // the inverse inter-pass twiddles of pass 0 carry n^-1: ifft needs no scaling sweep
-    int logR[NTT_MAX_PASSES] = { 0, 0, 0, 0 };
-    int logW[NTT_MAX_PASSES] = { 0, 0, 0, 0 };
-    void* consts = nullptr;                          // DomainConsts (device)
-    void* tw_inter[2][NTT_MAX_PASSES] = {};          // [inverse][pass]: omega_{N_q}^{i*lo}, N_q entries (passes 0..p-2)
-    void* tw_radix[2][NTT_MAX_PASSES] = {};          // [inverse][pass]: omega_{R_q}^j, R_q/2 entries
-    void* tw_radix29[2][NTT_MAX_PASSES] = {};        // the same entries times 32 (R'-form, canonical): multipliers of the 29-bit-limb pass kernel
-    uint64_t root_host[4] = { 0, 0, 0, 0 };          // host copy of the domain's root of unity (Montgomery form, canonical): poly.hip builds evaluation-point tables on the host
-    void* coset_fwd = nullptr;                       // g^j, j < n
-    void* coset_inv = nullptr;                       // n^-1 * g^-j, j < n
-    size_t bytes = 0;
-};
-
-// ---------------------------------------------------------------------------------------------- MSM
-struct Srs {
-    size_t n = 0;          // number of (plain) points
-    void* points = nullptr; // device: n affine points, 64 B each, Montgomery, canonical (= window 0 of a table below)
-    static constexpr int MAX_WIDTHS = 7; // BBG_MSM_TABLE_WIDTHS (msm_cfg.h)
-    void* tables[MAX_WIDTHS] = {}; // window tables T[w][i] = 2^(MsmCfg<C>::table_offset(w)) P_i (balanced windows, halved weight for the narrow ones: msm_cfg.h) per compiled width C (slot = msm_width_slot(C), msm.hip); built on first use
-    int home_slot = -1;    // the table built at registration: its window 0 IS `points`, so it is never released before the handle
-    int device = 0;
-    // tables[] may be read, built (first MSM of a width) and released (bbg_memory_trim of the owning context) from DIFFERENT contexts'
-    // threads: held from the choice of a table until every kernel that reads it is queued, and by the trim around its device
-    // synchronisation + free (lock order: bbg_ctx::mu -> g_srs_mu -> Srs::mu)
-    std::mutex mu;
-};
-
 // A grow-only device buffer: the one owner type of a context's (and a bbg_multi's) working memory.  No destructor frees it: its owner
 // is torn down explicitly (bbg_destroy, bbg_memory_trim) after hipSetDevice.
 struct DevBuf {
@@ -93,6 +56,57 @@ struct DevBuf {
         p = nullptr;
         bytes = 0;
     }
+};
+
+// ---------------------------------------------------------------------------------------------- NTT
+constexpr int NTT_MAX_PASSES = 4;
+// the pass-kernel families of ntt.hip, in the order of its dispatch table: the radix-2-in-LDS kernel, then the three radix-8 ones
+enum NttFamily { NTT_PASS = 0, NTT_PASS8, NTT_PASS8S, NTT_PASS29, NTT_FAMILIES };
+
+// Per-domain-size device tables: the GPU counterpart of evaluation_domain::compute_lookup_table()
+// (reference polynomials/evaluation_domain.cpp:33-55,169-175).  Built once per log2(n), cached in the context.
+struct NttDomain {
+    unsigned log2n = 0;
+    int passes = 0;
+    bool use_pass8 = false; // register-resident radix-8 pass kernel (ntt_pass8.hip.h) vs the radix-2-in-LDS one
+    int tile_log8 = 11;     // its tile: 2^11 elements (256 threads) or 2^12 (512 threads: 2^21 / 2^22 in two passes)
+    bool inv_scaled = false; // the inverse inter-pass twiddles of pass 0 carry n^-1: ifft needs no scaling sweep
+    int logR[NTT_MAX_PASSES] = { 0, 0, 0, 0 };
+    int logW[NTT_MAX_PASSES] = { 0, 0, 0, 0 };
+    DevBuf consts;                                   // DomainConsts
+    DevBuf tw_inter[2][NTT_MAX_PASSES];              // [inverse][pass]: omega_{N_q}^{i*lo}, N_q entries (passes 0..p-2)
+    DevBuf tw_radix[2][NTT_MAX_PASSES];              // [inverse][pass]: omega_{R_q}^j, R_q entries
+    DevBuf tw_radix29[2][NTT_MAX_PASSES];            // the same entries times 32 (R'-form, canonical): multipliers of the 29-bit-limb pass kernel
+    uint64_t root_host[4] = { 0, 0, 0, 0 };          // host copy of the domain's root of unity (Montgomery form, canonical): poly.hip builds evaluation-point tables on the host
+    DevBuf coset_fwd;                                // g^j, j < n
+    DevBuf coset_inv;                                // n^-1 * g^-j, j < n
+    // every device table of the domain (D: NttDomain, const or not): what ntt_free_domain releases and bbg_memory_report counts
+    template <class D, class F> static void each_table(D& d, F f)
+    {
+        f(d.consts), f(d.coset_fwd), f(d.coset_inv);
+        for (int inv = 0; inv < 2; inv++)
+            for (int q = 0; q < NTT_MAX_PASSES; q++) f(d.tw_inter[inv][q]), f(d.tw_radix[inv][q]), f(d.tw_radix29[inv][q]);
+    }
+    size_t bytes() const
+    {
+        size_t sum = 0;
+        each_table(*this, [&sum](const DevBuf& b) { sum += b.bytes; });
+        return sum;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------- MSM
+struct Srs {
+    size_t n = 0;          // number of (plain) points
+    void* points = nullptr; // device: n affine points, 64 B each, Montgomery, canonical (= window 0 of a table below)
+    static constexpr int MAX_WIDTHS = 7; // BBG_MSM_TABLE_WIDTHS (msm_cfg.h)
+    void* tables[MAX_WIDTHS] = {}; // window tables T[w][i] = 2^(MsmCfg<C>::table_offset(w)) P_i (balanced windows, halved weight for the narrow ones: msm_cfg.h) per compiled width C (slot = msm_width_slot(C), msm.hip); built on first use
+    int home_slot = -1;    // the table built at registration: its window 0 IS `points`, so it is never released before the handle
+    int device = 0;
+    // tables[] may be read, built (first MSM of a width) and released (bbg_memory_trim of the owning context) from DIFFERENT contexts'
+    // threads: held from the choice of a table until every kernel that reads it is queued, and by the trim around its device
+    // synchronisation + free (lock order: bbg_ctx::mu -> g_srs_mu -> Srs::mu)
+    std::mutex mu;
 };
 
 // Optional per-kernel timing with HIP events on the launch stream (bbg_profile_*): bench.py reads the average
@@ -170,9 +184,7 @@ struct bbg_ctx {
     int ntt_big_tile = 1;    // option "ntt_big_tile": 1 = 2^21 as TWO passes over 4096-element tiles instead of three over 2048; 2 = 2^22 as well; 0 = never
     int ntt_lds_planes = 0;  // option "ntt_lds_planes": 2 = the tile stays in LDS between two steps (k_ntt_pass8), 1 = it moves one 16-byte plane at a time (k_ntt_pass8s: half the LDS, three blocks per CU), 0 = automatic (1 from 2^22)
     int ntt_limbs29 = -1;    // option "ntt_limbs29": 1 = pass arithmetic on lazily reduced 9 x 29-bit limbs (k_ntt_pass29), 0 = 8 x 32-bit (k_ntt_pass8 / 8s), -1 = automatic
-    bool ntt_attr29_set = false;
-    bool ntt_attr8s_set = false;
-    bool ntt_attr8_set = false, ntt_attr_set = false; // dynamic-LDS attributes of the pass kernels set on this context's device
+    bool ntt_attr_set[bbg::NTT_FAMILIES] = {}; // dynamic-LDS attributes of a family's pass kernels set on this context's device
     // fixed_base.hip: the table T[w][d-1] = d 2^(8w) B of the base point last used (one slot: another base rebuilds it in place)
     bbg::DevBuf fb_table;
     uint64_t fb_table_key[8] = {}; // the base's canonical bytes

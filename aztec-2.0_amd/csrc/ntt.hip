@@ -499,15 +499,7 @@ static void plan_passes(bbg_ctx* ctx, NttDomain& d)
 
 void ntt_free_domain(NttDomain& d)
 {
-    if (d.consts) (void)hipFree(d.consts);
-    for (int inv = 0; inv < 2; inv++)
-        for (int q = 0; q < NTT_MAX_PASSES; q++) {
-            if (d.tw_inter[inv][q]) (void)hipFree(d.tw_inter[inv][q]);
-            if (d.tw_radix[inv][q]) (void)hipFree(d.tw_radix[inv][q]);
-            if (d.tw_radix29[inv][q]) (void)hipFree(d.tw_radix29[inv][q]);
-        }
-    if (d.coset_fwd) (void)hipFree(d.coset_fwd);
-    if (d.coset_inv) (void)hipFree(d.coset_inv);
+    NttDomain::each_table(d, [](DevBuf& b) { b.release(); });
     d = NttDomain();
 }
 
@@ -517,10 +509,9 @@ static int fill_domain(bbg_ctx* ctx, NttDomain& d)
     const unsigned log2n = d.log2n;
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << log2n;
-    BBG_HIP(hipMalloc(&d.consts, sizeof(DomainConsts)));
-    d.bytes += sizeof(DomainConsts);
-    hipLaunchKernelGGL(k_domain_init, dim3(1), dim3(64), 0, st, (DomainConsts*)d.consts, log2n);
-    DomainConsts* dc = (DomainConsts*)d.consts;
+    if (int rc = d.consts.ensure(sizeof(DomainConsts))) return rc;
+    DomainConsts* dc = (DomainConsts*)d.consts.p;
+    hipLaunchKernelGGL(k_domain_init, dim3(1), dim3(64), 0, st, dc, log2n);
     for (int inv = 0; inv < 2; inv++) {
         const Fr* pow2 = inv ? dc->pow2_root_inv : dc->pow2_root;
         int logS = (int)log2n;
@@ -529,41 +520,37 @@ static int fill_domain(bbg_ctx* ctx, NttDomain& d)
             logS -= logR;
             // radix twiddles w_R^j = w_n^(j * n/R)
             const size_t half = (size_t)1 << logR; // w_R^x for x < R (k_ntt_pass uses the first half, k_ntt_pass8 all of it)
-            BBG_HIP(hipMalloc(&d.tw_radix[inv][q], half * sizeof(Fr)));
-            d.bytes += half * sizeof(Fr);
-            hipLaunchKernelGGL(k_twiddle_1d, dim3(grid_for(half, 256)), dim3(256), 0, st, (Fr*)d.tw_radix[inv][q], pow2, half,
+            if (int rc = d.tw_radix[inv][q].ensure(half * sizeof(Fr))) return rc;
+            hipLaunchKernelGGL(k_twiddle_1d, dim3(grid_for(half, 256)), dim3(256), 0, st, (Fr*)d.tw_radix[inv][q].p, pow2, half,
                                (uint64_t)(n >> logR));
             if (d.use_pass8) { // the same table in R'-form, as 9-limb rows, for k_ntt_pass29 (R <= 2048 entries of 48 or 80 bytes)
-                BBG_HIP(hipMalloc(&d.tw_radix29[inv][q], half * NTT29_TW_ROW * 4));
-                d.bytes += half * NTT29_TW_ROW * 4;
-                hipLaunchKernelGGL(k_to_rprime, dim3(grid_for(half, 256)), dim3(256), 0, st, (uint32_t*)d.tw_radix29[inv][q], (const Fr*)d.tw_radix[inv][q], half,
+                if (int rc = d.tw_radix29[inv][q].ensure(half * NTT29_TW_ROW * 4)) return rc;
+                hipLaunchKernelGGL(k_to_rprime, dim3(grid_for(half, 256)), dim3(256), 0, st, (uint32_t*)d.tw_radix29[inv][q].p, (const Fr*)d.tw_radix[inv][q].p, half,
                                    p29_shoup(logR) != 0 ? 1 : 0);
             }
             if (q < d.passes - 1) {
                 // inter-pass twiddles w_{N_q}^(i*lo), N_q = R*S ; w_{N_q} = w_n^(n/N_q): use the pow2 table shifted
                 const int logN = logR + logS;
                 const size_t cnt = (size_t)1 << logN;
-                BBG_HIP(hipMalloc(&d.tw_inter[inv][q], cnt * sizeof(Fr)));
-                d.bytes += cnt * sizeof(Fr);
+                if (int rc = d.tw_inter[inv][q].ensure(cnt * sizeof(Fr))) return rc;
                 // w_{N_q}^(2^b) = w_n^(2^(b + log2n - logN))
                 // inverse direction: n^-1 rides on the first pass's inter-pass twiddles, so ifft costs exactly what fft costs
                 // (the reference scales in a separate sweep, polynomial_arithmetic.cpp:379-385)
                 const Fr* scale = (inv && q == 0) ? &dc->n_inv : nullptr;
-                hipLaunchKernelGGL(k_twiddle_2d, dim3(grid_for(cnt, 256)), dim3(256), 0, st, (Fr*)d.tw_inter[inv][q],
+                hipLaunchKernelGGL(k_twiddle_2d, dim3(grid_for(cnt, 256)), dim3(256), 0, st, (Fr*)d.tw_inter[inv][q].p,
                                    pow2 + (log2n - logN), logR, logS, scale);
             }
         }
     }
     // coset tables: g^j and n^-1 * g^-j
-    BBG_HIP(hipMalloc(&d.coset_fwd, n * sizeof(Fr)));
-    BBG_HIP(hipMalloc(&d.coset_inv, n * sizeof(Fr)));
-    d.bytes += 2 * n * sizeof(Fr);
+    if (int rc = d.coset_fwd.ensure(n * sizeof(Fr))) return rc;
+    if (int rc = d.coset_inv.ensure(n * sizeof(Fr))) return rc;
     hipLaunchKernelGGL(k_pow2_table, dim3(1), dim3(64), 0, st, dc->pow2_tmp, &dc->gen, (const Fr*)nullptr);
-    hipLaunchKernelGGL(k_powers, dim3(grid_for((n + POW_E - 1) / POW_E, 256)), dim3(256), 0, st, (Fr*)d.coset_fwd,
+    hipLaunchKernelGGL(k_powers, dim3(grid_for((n + POW_E - 1) / POW_E, 256)), dim3(256), 0, st, (Fr*)d.coset_fwd.p,
                        dc->pow2_tmp, (const Fr*)nullptr, n);
     hipLaunchKernelGGL(k_pow2_table, dim3(1), dim3(64), 0, st, dc->pow2_tmp, &dc->gen_inv, (const Fr*)nullptr);
     d.inv_scaled = d.passes > 1; // the inverse core already delivers n^-1 * (...) when it has an inter-pass twiddle table
-    hipLaunchKernelGGL(k_powers, dim3(grid_for((n + POW_E - 1) / POW_E, 256)), dim3(256), 0, st, (Fr*)d.coset_inv,
+    hipLaunchKernelGGL(k_powers, dim3(grid_for((n + POW_E - 1) / POW_E, 256)), dim3(256), 0, st, (Fr*)d.coset_inv.p,
                        dc->pow2_tmp, d.inv_scaled ? (const Fr*)nullptr : (const Fr*)&dc->n_inv, n);
     BBG_HIP(hipGetLastError());
     {
@@ -596,210 +583,152 @@ static int build_domain(bbg_ctx* ctx, unsigned log2n, NttDomain** out)
     return BBG_OK;
 }
 
-static int launch_pass(bbg_ctx* ctx, const NttDomain& d, int q, int inverse, const Fr* in, Fr* out, const Fr* post, hipStream_t st,
-                       const Fr* pre = nullptr, size_t pre_count = 0, size_t in_count = ~(size_t)0, int batch = 1, const Fr* const* in_b = nullptr,
-                       Fr* const* out_b = nullptr)
+// The compiled (log-radix, log-tile) shapes of the radix-8 pass kernels, written down once: every instantiation of k_ntt_pass8, k_ntt_pass8s
+// and k_ntt_pass29 comes from this list (a new radix or tile is one X(...) here).
+#ifdef BBG_NTT_FAST_AB // experiment builds only (build_ab/): k_ntt_pass29 at radix 2^7, 2^8, 2^10 alone -- n = 2^20, 2^22, 2^24 -- compiles in a fraction of the time
+#define BBG_NTT_SHAPES(X) X(7, P8_TILE_LOG) X(8, P8_TILE_LOG) X(10, P8_TILE_LOG) X(10, P8_TILE_LOG_BIG)
+#define BBG_NTT_SHAPE_ENTRY(R, T) { R, T, { {}, {}, { p29_launch<R, T>, p29_attr<R, T> } } },
+#else
+#define BBG_NTT_SHAPES(X)                                                                                                                          \
+    X(3, P8_TILE_LOG) X(4, P8_TILE_LOG) X(5, P8_TILE_LOG) X(6, P8_TILE_LOG) X(7, P8_TILE_LOG) X(8, P8_TILE_LOG) X(9, P8_TILE_LOG) X(10, P8_TILE_LOG) \
+    X(11, P8_TILE_LOG) X(10, P8_TILE_LOG_BIG) X(11, P8_TILE_LOG_BIG)
+#define BBG_NTT_SHAPE_ENTRY(R, T) { R, T, { { p8_launch<R, T>, p8_attr<R, T> }, { p8s_launch<R, T>, p8s_attr<R, T> }, { p29_launch<R, T>, p29_attr<R, T> } } },
+#endif
+struct PassFns {
+    void (*launch)(const PassParams&, size_t tiles, hipStream_t) = nullptr;
+    hipError_t (*attr)() = nullptr; // sets the dynamic-LDS limit of both flavours (row, column)
+};
+struct PassShape {
+    int logR, tile_log;
+    PassFns fam[NTT_FAMILIES - 1]; // NTT_PASS8, NTT_PASS8S, NTT_PASS29
+};
+static constexpr PassShape PASS_SHAPES[] = { BBG_NTT_SHAPES(BBG_NTT_SHAPE_ENTRY) };
+
+// THE rule for which family's kernel runs the passes of a domain: what launch_pass launches and bbg_ntt_plan reports
+static NttFamily pass_family(const bbg_ctx* ctx, const NttDomain& d)
+{
+    if (!d.use_pass8) return NTT_PASS;
+#ifndef BBG_NTT_FAST_AB
+    // the pass on lazily reduced 29-bit limbs (ntt_pass29.hip.h)
+    if (ctx->ntt_limbs29 == 1 || (ctx->ntt_limbs29 == -1 && NTT_LIMBS29_AUTO(d.log2n))) return NTT_PASS29;
+    // one-plane exchange (ntt_pass8.hip.h: k_ntt_pass8s: half the LDS, three waves per SIMD): automatic from 2^22 (measured there)
+    return ctx->ntt_lds_planes == 1 || (ctx->ntt_lds_planes == 0 && d.log2n >= 22) ? NTT_PASS8S : NTT_PASS8;
+#else
+    return NTT_PASS29;
+#endif
+}
+
+// what the first pass of a multi-pass pass8 plan can fuse into its load (can_fuse): a pre-scale table (pre[g], g < pre_count) and a
+// zero-extended input (only in[0 .. in_count) exists; the rest of the domain is zero)
+struct FusedLoad {
+    const Fr* pre = nullptr;
+    size_t pre_count = 0;
+    size_t in_count = ~(size_t)0;
+    bool any() const { return pre != nullptr || in_count != ~(size_t)0; }
+};
+
+// pass q of `count` (1 .. 4) transforms of one domain, in[k] -> out[k], as one launch (grid.y = count)
+static int launch_pass(bbg_ctx* ctx, const NttDomain& d, int q, int inverse, int count, const Fr* const* in, Fr* const* out, const FusedLoad& load,
+                       const Fr* post, hipStream_t st)
 {
     PassParams p;
-    p.in = in;
-    p.out = out;
-    p.batch = batch;
-    if (batch > 1) {
-        p.in = in_b[0];
-        p.out = out_b[0];
-    }
-    p.in_b1 = batch > 1 ? in_b[1] : nullptr;
-    p.out_b1 = batch > 1 ? out_b[1] : nullptr;
-    p.in_b2 = batch > 2 ? in_b[2] : nullptr;
-    p.out_b2 = batch > 2 ? out_b[2] : nullptr;
-    p.in_b3 = batch > 3 ? in_b[3] : nullptr;
-    p.out_b3 = batch > 3 ? out_b[3] : nullptr;
-    p.pre = pre;
-    p.pre_count = pre_count;
-    p.in_count = in_count;
+    p.batch = count;
+    p.in = in[0];
+    p.out = out[0];
+    p.in_b1 = count > 1 ? in[1] : nullptr;
+    p.out_b1 = count > 1 ? out[1] : nullptr;
+    p.in_b2 = count > 2 ? in[2] : nullptr;
+    p.out_b2 = count > 2 ? out[2] : nullptr;
+    p.in_b3 = count > 3 ? in[3] : nullptr;
+    p.out_b3 = count > 3 ? out[3] : nullptr;
+    p.pre = load.pre;
+    p.pre_count = load.pre_count;
+    p.in_count = load.in_count;
     p.logR = d.logR[q];
     p.logW = d.logW[q];
     p.log2n = (int)d.log2n;
-    p.tw_radix = (const Fr*)d.tw_radix[inverse][q];
-    p.tw_radix29 = (const uint32_t*)d.tw_radix29[inverse][q];
+    p.tw_radix = (const Fr*)d.tw_radix[inverse][q].p;
+    p.tw_radix29 = (const uint32_t*)d.tw_radix29[inverse][q].p;
     p.post = post;
     p.row_pass = (q == d.passes - 1);
     int logS = (int)d.log2n;
     for (int k = 0; k <= q; k++) logS -= d.logR[k];
     p.logS = logS;
-    p.tw_inter = p.row_pass ? nullptr : (const Fr*)d.tw_inter[inverse][q];
+    p.tw_inter = p.row_pass ? nullptr : (const Fr*)d.tw_inter[inverse][q].p;
     p.logR1 = d.passes > 1 ? d.logR[0] : 0;
     p.nmid = d.passes >= 2 ? d.passes - 2 : 0;
     p.logMid[0] = d.passes >= 3 ? d.logR[1] : 0;
     p.logMid[1] = d.passes >= 4 ? d.logR[2] : 0;
-    const int R = 1 << p.logR, W = 1 << p.logW;
-    const size_t lds_bytes = ((size_t)2 * W * (R + 1) + R) * 16 + 64;
     const size_t tiles = ((size_t)1 << d.log2n) >> (p.logR + p.logW);
-#ifdef BBG_NTT_FAST_AB // experiment builds only (build_ab/): k_ntt_pass29 at radix 2^7, 2^8, 2^10 alone -- n = 2^20, 2^22, 2^24 -- compiles in a fraction of the time
-    if (d.use_pass8) {
-        bool& attr29 = ctx->ntt_attr29_set;
-        if (!attr29) {
-            BBG_HIP(p29_attr<7>()); BBG_HIP(p29_attr<8>()); BBG_HIP(p29_attr<10>()); BBG_HIP((p29_attr<10, P8_TILE_LOG_BIG>()));
-            attr29 = true;
-        }
-        ProfScope ps(ctx, "ntt_pass", st);
-        if (d.tile_log8 == P8_TILE_LOG && p.logR == 10) p29_launch<10>(p, tiles, st);
-        else if (d.tile_log8 == P8_TILE_LOG_BIG && p.logR == 10) p29_launch<10, P8_TILE_LOG_BIG>(p, tiles, st);
-        else if (d.tile_log8 == P8_TILE_LOG && p.logR == 8) p29_launch<8>(p, tiles, st);
-        else if (d.tile_log8 == P8_TILE_LOG && p.logR == 7) p29_launch<7>(p, tiles, st);
-        else { set_error("ntt: BBG_NTT_FAST_AB build (radix 2^7, 2^8, 2^10 passes only: 2^20, 2^22, 2^24)"); return BBG_E_INVALID; }
-        return BBG_OK;
-    }
-#else
-    if (d.use_pass8) {
-        bool& attr8 = ctx->ntt_attr8_set; // hipFuncSetAttribute is per device: the flag lives in the context, not in a process-wide static
-        if (!attr8) {
-            BBG_HIP(p8_attr<3>()); BBG_HIP(p8_attr<4>()); BBG_HIP(p8_attr<5>()); BBG_HIP(p8_attr<6>()); BBG_HIP(p8_attr<7>());
-            BBG_HIP(p8_attr<8>()); BBG_HIP(p8_attr<9>()); BBG_HIP(p8_attr<10>()); BBG_HIP(p8_attr<11>());
-            BBG_HIP((p8_attr<10, P8_TILE_LOG_BIG>())); BBG_HIP((p8_attr<11, P8_TILE_LOG_BIG>()));
-            attr8 = true;
-        }
-        ProfScope ps(ctx, "ntt_pass", st);
-        if (ctx->ntt_limbs29 == 1 || (ctx->ntt_limbs29 == -1 && NTT_LIMBS29_AUTO(d.log2n))) { // the pass on lazily reduced 29-bit limbs (ntt_pass29.hip.h)
-            bool& attr29 = ctx->ntt_attr29_set;
-            if (!attr29) {
-                BBG_HIP(p29_attr<3>()); BBG_HIP(p29_attr<4>()); BBG_HIP(p29_attr<5>()); BBG_HIP(p29_attr<6>()); BBG_HIP(p29_attr<7>());
-                BBG_HIP(p29_attr<8>()); BBG_HIP(p29_attr<9>()); BBG_HIP(p29_attr<10>()); BBG_HIP(p29_attr<11>());
-                BBG_HIP((p29_attr<10, P8_TILE_LOG_BIG>())); BBG_HIP((p29_attr<11, P8_TILE_LOG_BIG>()));
-                attr29 = true;
-            }
-            if (d.tile_log8 == P8_TILE_LOG_BIG) {
-                if (p.logR == 11) p29_launch<11, P8_TILE_LOG_BIG>(p, tiles, st);
-                else if (p.logR == 10) p29_launch<10, P8_TILE_LOG_BIG>(p, tiles, st);
-                else { set_error("ntt: bad pass8 radix for the 4096-element tile"); return BBG_E_INVALID; }
-                return BBG_OK;
-            }
-            switch (p.logR) {
-            case 3: p29_launch<3>(p, tiles, st); break;
-            case 4: p29_launch<4>(p, tiles, st); break;
-            case 5: p29_launch<5>(p, tiles, st); break;
-            case 6: p29_launch<6>(p, tiles, st); break;
-            case 7: p29_launch<7>(p, tiles, st); break;
-            case 8: p29_launch<8>(p, tiles, st); break;
-            case 9: p29_launch<9>(p, tiles, st); break;
-            case 10: p29_launch<10>(p, tiles, st); break;
-            case 11: p29_launch<11>(p, tiles, st); break;
-            default: set_error("ntt: bad pass8 radix"); return BBG_E_INVALID;
-            }
-            return BBG_OK;
-        }
-        // one-plane exchange (ntt_pass8.hip.h: k_ntt_pass8s: half the LDS, three waves per SIMD): automatic from 2^22 (measured there)
-        if (ctx->ntt_lds_planes == 1 || (ctx->ntt_lds_planes == 0 && d.log2n >= 22)) {
-            bool& attr8s = ctx->ntt_attr8s_set;
-            if (!attr8s) {
-                BBG_HIP(p8s_attr<3>()); BBG_HIP(p8s_attr<4>()); BBG_HIP(p8s_attr<5>()); BBG_HIP(p8s_attr<6>()); BBG_HIP(p8s_attr<7>());
-                BBG_HIP(p8s_attr<8>()); BBG_HIP(p8s_attr<9>()); BBG_HIP(p8s_attr<10>()); BBG_HIP(p8s_attr<11>());
-                BBG_HIP((p8s_attr<10, P8_TILE_LOG_BIG>())); BBG_HIP((p8s_attr<11, P8_TILE_LOG_BIG>()));
-                attr8s = true;
-            }
-            if (d.tile_log8 == P8_TILE_LOG_BIG) {
-                if (p.logR == 11) p8s_launch<11, P8_TILE_LOG_BIG>(p, tiles, st);
-                else if (p.logR == 10) p8s_launch<10, P8_TILE_LOG_BIG>(p, tiles, st);
-                else { set_error("ntt: bad pass8 radix for the 4096-element tile"); return BBG_E_INVALID; }
-                return BBG_OK;
-            }
-            switch (p.logR) {
-            case 3: p8s_launch<3>(p, tiles, st); break;
-            case 4: p8s_launch<4>(p, tiles, st); break;
-            case 5: p8s_launch<5>(p, tiles, st); break;
-            case 6: p8s_launch<6>(p, tiles, st); break;
-            case 7: p8s_launch<7>(p, tiles, st); break;
-            case 8: p8s_launch<8>(p, tiles, st); break;
-            case 9: p8s_launch<9>(p, tiles, st); break;
-            case 10: p8s_launch<10>(p, tiles, st); break;
-            case 11: p8s_launch<11>(p, tiles, st); break;
-            default: set_error("ntt: bad pass8 radix"); return BBG_E_INVALID;
-            }
-            return BBG_OK;
-        }
-        if (d.tile_log8 == P8_TILE_LOG_BIG) {
-            if (p.logR == 11) p8_launch<11, P8_TILE_LOG_BIG>(p, tiles, st);
-            else if (p.logR == 10) p8_launch<10, P8_TILE_LOG_BIG>(p, tiles, st);
-            else { set_error("ntt: bad pass8 radix for the 4096-element tile"); return BBG_E_INVALID; }
-            return BBG_OK;
-        }
-        switch (p.logR) {
-        case 3: p8_launch<3>(p, tiles, st); break;
-        case 4: p8_launch<4>(p, tiles, st); break;
-        case 5: p8_launch<5>(p, tiles, st); break;
-        case 6: p8_launch<6>(p, tiles, st); break;
-        case 7: p8_launch<7>(p, tiles, st); break;
-        case 8: p8_launch<8>(p, tiles, st); break;
-        case 9: p8_launch<9>(p, tiles, st); break;
-        case 10: p8_launch<10>(p, tiles, st); break;
-        case 11: p8_launch<11>(p, tiles, st); break;
-        default: set_error("ntt: bad pass8 radix"); return BBG_E_INVALID;
-        }
-        return BBG_OK;
-    }
-#endif
-    bool& attr_set = ctx->ntt_attr_set;
-    if (!attr_set) {
-        BBG_HIP(hipFuncSetAttribute((const void*)k_ntt_pass, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const NttFamily fam = pass_family(ctx, d);
+    bool& attr_set = ctx->ntt_attr_set[fam]; // hipFuncSetAttribute is per device: the flags live in the context, not in a process-wide static
+    if (fam == NTT_PASS) {
+        if (!attr_set) BBG_HIP(hipFuncSetAttribute((const void*)k_ntt_pass, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
+        const int R = 1 << p.logR, W = 1 << p.logW;
+        const size_t lds_bytes = ((size_t)2 * W * (R + 1) + R) * 16 + 64;
+        const int threads = std::min(std::max((R * W) / 2, 64), 1024);
+        ProfScope ps(ctx, "ntt_pass", st);
+        hipLaunchKernelGGL(k_ntt_pass, dim3((unsigned)tiles, (unsigned)count), dim3(threads), lds_bytes, st, p);
+        return BBG_OK;
     }
-    int threads = (R * W) / 2;
-    if (threads > 1024) threads = 1024;
-    if (threads < 64) threads = 64;
+    const PassFns* fns = nullptr;
+    for (const PassShape& s : PASS_SHAPES)
+        if (s.logR == p.logR && s.tile_log == d.tile_log8) fns = &s.fam[fam - NTT_PASS8];
+    if (!fns || !fns->launch) {
+        set_error("ntt: no pass kernel compiled for log-radix " + std::to_string(p.logR) + " on the 2^" + std::to_string(d.tile_log8) + "-element tile");
+        return BBG_E_INVALID;
+    }
+    if (!attr_set)
+        for (const PassShape& s : PASS_SHAPES)
+            if (s.fam[fam - NTT_PASS8].attr) BBG_HIP(s.fam[fam - NTT_PASS8].attr());
+    attr_set = true;
     ProfScope ps(ctx, "ntt_pass", st);
-    hipLaunchKernelGGL(k_ntt_pass, dim3((unsigned)tiles, (unsigned)(p.batch > 1 ? p.batch : 1)), dim3(threads), lds_bytes, st, p);
+    fns->launch(p, tiles, st);
     return BBG_OK;
 }
 
-// core transform: `in` -> `out` (may be the same array); `post` (optional) multiplies natural-index outputs.
-// Multi-pass pass8 plans also take, fused into the first pass's load: a pre-scale table (pre[g], g < pre_count) and a zero-extended
-// input (only in[0 .. in_count) exists; the rest of the domain is zero).  can_fuse(d) says whether the plan supports that.
+// core transform: `count` (<= 4) independent transforms of ONE domain through the same launches (grid.y = count), in[k] -> out[k] (may be
+// the same array); `post` (optional) multiplies natural-index outputs.  More than one at once is for domains whose single transform
+// leaves most of the chip idle (2^18: 128 tiles for 256 CUs).  Multi-pass pass8 plans also take a FusedLoad; can_fuse(d) says whether
+// the plan supports that.
 static bool can_fuse(const NttDomain& d) { return d.use_pass8 && d.passes > 1; }
-static int ntt_core(bbg_ctx* ctx, NttDomain& d, const Fr* in, Fr* out, int inverse, const Fr* post, hipStream_t st, const Fr* pre = nullptr,
-                    size_t pre_count = 0, size_t in_count = ~(size_t)0)
+static int ntt_core_batch(bbg_ctx* ctx, NttDomain& d, int count, const Fr* const* in, Fr* const* out, int inverse, const Fr* post, hipStream_t st,
+                          const FusedLoad& load = {})
 {
+    if (count < 1 || count > 4 || (count > 1 && d.log2n == 0)) { set_error("ntt_core_batch: 1 .. 4 transforms of a domain of at least two points"); return BBG_E_INVALID; }
     const size_t n = (size_t)1 << d.log2n;
     if (d.log2n == 0) {
-        if (in != out) BBG_HIP(hipMemcpyAsync(out, in, sizeof(Fr), hipMemcpyDeviceToDevice, st));
-        if (post) hipLaunchKernelGGL(k_scale_table, dim3(1), dim3(64), 0, st, out, post, (size_t)1);
+        if (in[0] != out[0]) BBG_HIP(hipMemcpyAsync(out[0], in[0], sizeof(Fr), hipMemcpyDeviceToDevice, st));
+        if (post) hipLaunchKernelGGL(k_scale_table, dim3(1), dim3(64), 0, st, out[0], post, (size_t)1);
         return BBG_OK;
     }
     if (d.passes == 1) {
         // a single-pass plan has no fused pre-scale and no zero-extended input: callers ask can_fuse() first; one that did not gets an error,
         // not an unscaled transform that reads past in_count
-        if (pre != nullptr || in_count != ~(size_t)0) { set_error("ntt_core: this plan does not fuse a pre-scale table or a zero-extended input (can_fuse)"); return BBG_E_INVALID; }
-        return launch_pass(ctx, d, 0, inverse, in, out, post, st);
-    }
-    int rc = ctx->ntt_scratch.ensure(n * sizeof(Fr));
-    if (rc) return rc;
-    Fr* scratch = (Fr*)ctx->ntt_scratch.p;
-    // pass 0: in -> scratch (same positions); middle passes in place on scratch; last pass scratch -> out (transposing)
-    rc = launch_pass(ctx, d, 0, inverse, in, scratch, nullptr, st, pre, pre_count, in_count);
-    for (int q = 1; q < d.passes - 1 && !rc; q++) rc = launch_pass(ctx, d, q, inverse, scratch, scratch, nullptr, st);
-    if (!rc) rc = launch_pass(ctx, d, d.passes - 1, inverse, scratch, out, post, st);
-    return rc;
-}
-
-// `count` (<= 4) independent transforms of ONE domain through the same launches (grid.y = count): what ntt_core does, for each k, with in[k]
-// -> out[k].  For domains whose single transform leaves most of the chip idle (2^18: 128 tiles for 256 CUs).
-static int ntt_core_batch(bbg_ctx* ctx, NttDomain& d, int count, const Fr* const* in, Fr* const* out, int inverse, const Fr* post, hipStream_t st,
-                          const Fr* pre = nullptr, size_t pre_count = 0, size_t in_count = ~(size_t)0)
-{
-    if (count == 1) return ntt_core(ctx, d, in[0], out[0], inverse, post, st, pre, pre_count, in_count);
-    if (count < 1 || count > 4 || d.log2n == 0) { set_error("ntt_core_batch: 1 .. 4 transforms of a domain of at least two points"); return BBG_E_INVALID; }
-    const size_t n = (size_t)1 << d.log2n;
-    if (d.passes == 1) {
-        if (pre != nullptr || in_count != ~(size_t)0) { set_error("ntt_core_batch: this plan does not fuse a pre-scale table or a zero-extended input (can_fuse)"); return BBG_E_INVALID; }
-        return launch_pass(ctx, d, 0, inverse, nullptr, nullptr, post, st, nullptr, 0, ~(size_t)0, count, in, out);
+        if (load.any()) { set_error(std::string(count == 1 ? "ntt_core" : "ntt_core_batch") + ": this plan does not fuse a pre-scale table or a zero-extended input (can_fuse)"); return BBG_E_INVALID; }
+        return launch_pass(ctx, d, 0, inverse, count, in, out, {}, post, st);
     }
     int rc = ctx->ntt_scratch.ensure((size_t)count * n * sizeof(Fr));
     if (rc) return rc;
     Fr* scratch[4] = { nullptr, nullptr, nullptr, nullptr };
     for (int k = 0; k < count; k++) scratch[k] = (Fr*)ctx->ntt_scratch.p + (size_t)k * n;
-    rc = launch_pass(ctx, d, 0, inverse, nullptr, nullptr, nullptr, st, pre, pre_count, in_count, count, in, scratch);
-    for (int q = 1; q < d.passes - 1 && !rc; q++) rc = launch_pass(ctx, d, q, inverse, nullptr, nullptr, nullptr, st, nullptr, 0, ~(size_t)0, count, scratch, scratch);
-    if (!rc) rc = launch_pass(ctx, d, d.passes - 1, inverse, nullptr, nullptr, post, st, nullptr, 0, ~(size_t)0, count, scratch, out);
+    // pass 0: in -> scratch (same positions); middle passes in place on scratch; last pass scratch -> out (transposing)
+    rc = launch_pass(ctx, d, 0, inverse, count, in, scratch, load, nullptr, st);
+    for (int q = 1; q < d.passes - 1 && !rc; q++) rc = launch_pass(ctx, d, q, inverse, count, scratch, scratch, {}, nullptr, st);
+    if (!rc) rc = launch_pass(ctx, d, d.passes - 1, inverse, count, scratch, out, {}, post, st);
     return rc;
+}
+static int ntt_core(bbg_ctx* ctx, NttDomain& d, const Fr* in, Fr* out, int inverse, const Fr* post, hipStream_t st, const FusedLoad& load = {})
+{
+    return ntt_core_batch(ctx, d, 1, &in, &out, inverse, post, st, load);
+}
+
+// the inverse core's n^-1 where no inter-pass twiddle table carries it (single-pass domains): a[j] *= n^-1
+static void scale_n_inv(const NttDomain& d, Fr* a, hipStream_t st)
+{
+    const size_t n = (size_t)1 << d.log2n;
+    if (!d.inv_scaled) hipLaunchKernelGGL(k_scale_const, dim3(grid_for(n, 256)), dim3(256), 0, st, a, &((DomainConsts*)d.consts.p)->n_inv, n);
 }
 
 // The prover's FFT work item without its copies (work_queue.hpp:252-264): the n_in coefficients at d_in, zero-extended to the 2^log2n
@@ -812,7 +741,7 @@ int ntt_coset_extend(bbg_ctx* ctx, const void* d_in, size_t n_in, void* d_out, u
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
     const size_t n = (size_t)1 << log2n;
-    if (can_fuse(*dp)) return ntt_core(ctx, *dp, (const Fr*)d_in, (Fr*)d_out, 0, nullptr, st, (const Fr*)dp->coset_fwd, n_in, n_in);
+    if (can_fuse(*dp)) return ntt_core(ctx, *dp, (const Fr*)d_in, (Fr*)d_out, 0, nullptr, st, { (const Fr*)dp->coset_fwd.p, n_in, n_in });
     BBG_HIP(hipMemcpyAsync(d_out, d_in, n_in * 32, hipMemcpyDeviceToDevice, st));
     if (n > n_in) BBG_HIP(hipMemsetAsync((char*)d_out + n_in * 32, 0, (n - n_in) * 32, st));
     return ntt_run(ctx, d_out, log2n, BBG_COSET_FFT, n_in, nullptr, st);
@@ -832,8 +761,7 @@ int ntt_ifft_to(bbg_ctx* ctx, const void* d_in, void* d_out, unsigned log2n, hip
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
     rc = ntt_core(ctx, *dp, (const Fr*)d_in, (Fr*)d_out, 1, nullptr, st);
-    if (!rc && !dp->inv_scaled)
-        hipLaunchKernelGGL(k_scale_const, dim3(grid_for(n, 256)), dim3(256), 0, st, (Fr*)d_out, &((DomainConsts*)dp->consts)->n_inv, n);
+    if (!rc) scale_n_inv(*dp, (Fr*)d_out, st);
     return rc;
 }
 
@@ -851,10 +779,8 @@ int ntt_ifft_to_batch(bbg_ctx* ctx, int count, const void* const* d_in, void* co
     NttDomain* dp = nullptr;
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
-    const size_t n = (size_t)1 << log2n;
     rc = ntt_core_batch(ctx, *dp, count, (const Fr* const*)d_in, (Fr* const*)d_out, 1, nullptr, st);
-    for (int k = 0; k < count && !rc && !dp->inv_scaled; k++)
-        hipLaunchKernelGGL(k_scale_const, dim3(grid_for(n, 256)), dim3(256), 0, st, (Fr*)d_out[k], &((DomainConsts*)dp->consts)->n_inv, n);
+    for (int k = 0; k < count && !rc; k++) scale_n_inv(*dp, (Fr*)d_out[k], st);
     return rc;
 }
 // ntt_coset_extend for `count` (<= 4) inputs of the same length at once
@@ -865,7 +791,7 @@ int ntt_coset_extend_batch(bbg_ctx* ctx, int count, const void* const* d_in, siz
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
     if (count > 1 && can_fuse(*dp) && n_in <= ((size_t)1 << log2n))
-        return ntt_core_batch(ctx, *dp, count, (const Fr* const*)d_in, (Fr* const*)d_out, 0, nullptr, st, (const Fr*)dp->coset_fwd, n_in, n_in);
+        return ntt_core_batch(ctx, *dp, count, (const Fr* const*)d_in, (Fr* const*)d_out, 0, nullptr, st, { (const Fr*)dp->coset_fwd.p, n_in, n_in });
     for (int k = 0; k < count; k++) {
         rc = ntt_coset_extend(ctx, d_in[k], n_in, d_out[k], log2n, st);
         if (rc) return rc;
@@ -880,7 +806,7 @@ int ntt_coset_ifft_scaled(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, const vo
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
     if (!can_fuse(*dp)) return BBG_E_NOFUSE;
-    return ntt_core(ctx, *dp, (Fr*)d_coeffs, (Fr*)d_coeffs, 1, (const Fr*)dp->coset_inv, st, (const Fr*)d_scale, (size_t)1 << log2n);
+    return ntt_core(ctx, *dp, (Fr*)d_coeffs, (Fr*)d_coeffs, 1, (const Fr*)dp->coset_inv.p, st, { (const Fr*)d_scale, (size_t)1 << log2n });
 }
 
 int ntt_run(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, int op, size_t generator_size, const uint64_t* constant,
@@ -894,7 +820,7 @@ int ntt_run(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, int op, size_t generat
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
     NttDomain& d = *dp;
-    DomainConsts* dc = (DomainConsts*)d.consts;
+    DomainConsts* dc = (DomainConsts*)d.consts.p;
     const size_t n = (size_t)1 << log2n;
     if (generator_size == 0 || generator_size > n) generator_size = n;
     Fr* a = (Fr*)d_coeffs;
@@ -909,19 +835,19 @@ int ntt_run(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, int op, size_t generat
         break;
     case BBG_IFFT:
         rc = ntt_core(ctx, d, a, a, 1, nullptr, st);
-        if (!rc && !d.inv_scaled) hipLaunchKernelGGL(k_scale_const, dim3(grid_for(n, 256)), dim3(256), 0, st, a, &dc->n_inv, n);
+        if (!rc) scale_n_inv(d, a, st);
         break;
     case BBG_COSET_FFT:
         if (can_fuse(d)) { // a_j *= g^j (j < generator_size) as the first pass loads a_j
-            rc = ntt_core(ctx, d, a, a, 0, nullptr, st, (const Fr*)d.coset_fwd, generator_size);
+            rc = ntt_core(ctx, d, a, a, 0, nullptr, st, { (const Fr*)d.coset_fwd.p, generator_size });
             break;
         }
-        hipLaunchKernelGGL(k_scale_table, dim3(grid_for(generator_size, 256)), dim3(256), 0, st, a, (const Fr*)d.coset_fwd,
+        hipLaunchKernelGGL(k_scale_table, dim3(grid_for(generator_size, 256)), dim3(256), 0, st, a, (const Fr*)d.coset_fwd.p,
                            generator_size);
         rc = ntt_core(ctx, d, a, a, 0, nullptr, st);
         break;
     case BBG_COSET_IFFT:
-        rc = ntt_core(ctx, d, a, a, 1, (const Fr*)d.coset_inv, st); // the table carries n^-1 g^-j, or g^-j when the core delivers n^-1
+        rc = ntt_core(ctx, d, a, a, 1, (const Fr*)d.coset_inv.p, st); // the table carries n^-1 g^-j, or g^-j when the core delivers n^-1
         break;
     case BBG_FFT_WITH_CONSTANT:
         rc = ntt_core(ctx, d, a, a, 0, nullptr, st);
@@ -944,7 +870,7 @@ int ntt_run(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, int op, size_t generat
     case BBG_IFFT_WITH_CONSTANT:
         rc = ntt_core(ctx, d, a, a, 1, nullptr, st);
         if (!rc) {
-            if (!d.inv_scaled) hipLaunchKernelGGL(k_scale_const, dim3(grid_for(n, 256)), dim3(256), 0, st, a, &dc->n_inv, n);
+            scale_n_inv(d, a, st);
             hipLaunchKernelGGL(k_scale_const, dim3(grid_for(n, 256)), dim3(256), 0, st, a, cst, n);
         }
         break;
@@ -969,8 +895,8 @@ int ntt_coset_split(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, size_t ext, hi
     if (rc) return rc;
     const size_t n = (size_t)1 << log2n;
     Fr* a = (Fr*)d_coeffs;
-    DomainConsts* dcs = (DomainConsts*)dsmall->consts;
-    DomainConsts* dcl = (DomainConsts*)dlarge->consts;
+    DomainConsts* dcs = (DomainConsts*)dsmall->consts.p;
+    DomainConsts* dcl = (DomainConsts*)dlarge->consts.p;
     // replicate the n coefficients into ext slots, scale slot k by (g * w_{ext n}^k)^j, transform each, interleave
     hipLaunchKernelGGL(k_replicate, dim3(grid_for(n, 256)), dim3(256), 0, st, a, (int)log2n, (int)ext);
     // generator of slot k: g * root_large^k ; build incrementally in pow2_tmp[30] of the small domain
@@ -1051,7 +977,7 @@ int ntt_scale_powers(bbg_ctx* ctx, void* d_a, size_t count, const uint64_t* star
     NttDomain* dp = nullptr;
     int rc = build_domain(ctx, 0, &dp); // the size-1 domain only lends its scratch constants block
     if (rc) return rc;
-    DomainConsts* dc = (DomainConsts*)dp->consts;
+    DomainConsts* dc = (DomainConsts*)dp->consts.p;
     hipLaunchKernelGGL(k_set_fr, dim3(1), dim3(1), 0, st, &dc->gk, fr_arg(base));
     if (start) hipLaunchKernelGGL(k_set_fr, dim3(1), dim3(1), 0, st, &dc->constant, fr_arg(start));
     hipLaunchKernelGGL(k_pow2_table, dim3(1), dim3(64), 0, st, dc->pow2_tmp, (const Fr*)&dc->gk, (const Fr*)nullptr);
@@ -1097,10 +1023,10 @@ int ntt_scale_geometric(bbg_ctx* ctx, void* d_a, size_t count, unsigned log2n, i
     if (!rc) rc = build_domain(ctx, 0, &d0); // lends its scratch table
     if (!rc && mul_inv_log2 >= 0) rc = build_domain(ctx, (unsigned)mul_inv_log2, &dm);
     if (rc) return rc;
-    DomainConsts* dc = (DomainConsts*)dp->consts;
-    DomainConsts* sc = (DomainConsts*)d0->consts;
+    DomainConsts* dc = (DomainConsts*)dp->consts.p;
+    DomainConsts* sc = (DomainConsts*)d0->consts.p;
     const Fr* base = which_base == 0 ? &dc->gen : which_base == 1 ? &dc->gen_inv : which_base == 2 ? &dc->root : &dc->root_inv;
-    const Fr* mul = dm ? &((DomainConsts*)dm->consts)->n_inv : nullptr;
+    const Fr* mul = dm ? &((DomainConsts*)dm->consts.p)->n_inv : nullptr;
     hipLaunchKernelGGL(k_geometric_setup, dim3(1), dim3(64), 0, st, sc->pow2_tmp, &sc->gk, base, step, e0, mul);
     hipLaunchKernelGGL(k_scale_powers, dim3(grid_for((count + POW_E - 1) / POW_E, 256)), dim3(256), 0, st, (Fr*)d_a, sc->pow2_tmp, (const Fr*)&sc->gk, count);
     BBG_HIP(hipGetLastError());
@@ -1114,7 +1040,7 @@ int ntt_root_pow(bbg_ctx* ctx, unsigned log2n, uint64_t e, int inverse, uint64_t
     NttDomain* dp = nullptr;
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
-    DomainConsts* dc = (DomainConsts*)dp->consts;
+    DomainConsts* dc = (DomainConsts*)dp->consts.p;
     hipLaunchKernelGGL(k_fr_pow, dim3(1), dim3(64), 0, st, &dc->gk, inverse ? &dc->root_inv : &dc->root, e);
     BBG_HIP(hipMemcpyAsync(out, &dc->gk, 32, hipMemcpyDeviceToHost, st));
     BBG_HIP(hipStreamSynchronize(st));
@@ -1126,7 +1052,7 @@ int ntt_fr_pow(bbg_ctx* ctx, const uint64_t* base, uint64_t e, uint64_t* out, hi
     NttDomain* dp = nullptr;
     int rc = build_domain(ctx, 0, &dp);
     if (rc) return rc;
-    DomainConsts* dc = (DomainConsts*)dp->consts;
+    DomainConsts* dc = (DomainConsts*)dp->consts.p;
     hipLaunchKernelGGL(k_set_fr, dim3(1), dim3(1), 0, st, &dc->constant, fr_arg(base));
     hipLaunchKernelGGL(k_fr_pow, dim3(1), dim3(64), 0, st, &dc->gk, (const Fr*)&dc->constant, e);
     BBG_HIP(hipMemcpyAsync(out, &dc->gk, 32, hipMemcpyDeviceToHost, st));
@@ -1142,7 +1068,7 @@ int ntt_cross_dft(bbg_ctx* ctx, const void* d_in, void* d_out, unsigned log2G, s
     NttDomain* dp = nullptr;
     int rc = build_domain(ctx, log2n, &dp);
     if (rc) return rc;
-    DomainConsts* dc = (DomainConsts*)dp->consts;
+    DomainConsts* dc = (DomainConsts*)dp->consts.p;
     // w_G^j = w_n^(j * n/G): reuse the twiddle generator into pow2_tmp[0..G)
     const Fr* pow2 = inverse ? dc->pow2_root_inv : dc->pow2_root;
     hipLaunchKernelGGL(k_twiddle_1d, dim3(1), dim3(64), 0, st, dc->pow2_tmp, pow2, (size_t)1 << log2G, (uint64_t)(((size_t)1 << log2n) >> log2G));
@@ -1163,7 +1089,7 @@ int ntt_domain_consts(bbg_ctx* ctx, unsigned log2n, void** consts)
     NttDomain* d = nullptr;
     int rc = build_domain(ctx, log2n, &d);
     if (rc) return rc;
-    *consts = d->consts;
+    *consts = d->consts.p;
     return BBG_OK;
 }
 
@@ -1177,30 +1103,22 @@ int ntt_domain_root_host(bbg_ctx* ctx, unsigned log2n, uint64_t out[4])
     return BBG_OK;
 }
 
-// bbg_ntt_plan: the passes a 2^log2n transform runs as NOW (options included) and which pass kernel executes them -- the selection
-// logic of launch_pass restated on the plan, without building tables.  kernel: 0 = k_ntt_pass (radix 2 in LDS), 8 = k_ntt_pass8,
-// 81 = k_ntt_pass8s (one-plane exchange), 29 = k_ntt_pass29 (lazily reduced 9 x 29-bit limbs)
+// bbg_ntt_plan: the passes a 2^log2n transform runs as NOW (options included) and which pass kernel executes them -- plan_passes and
+// pass_family themselves, the functions a transform goes through, without building tables.  kernel: 0 = k_ntt_pass (radix 2 in LDS),
+// 8 = k_ntt_pass8, 81 = k_ntt_pass8s (one-plane exchange), 29 = k_ntt_pass29 (lazily reduced 9 x 29-bit limbs)
 int ntt_plan(bbg_ctx* ctx, unsigned log2n, int* passes, int* log_radix, int* kernel, int* tile_log)
 {
     if (log2n > 28) { set_error("bbg_ntt_plan: log2n > 28"); return BBG_E_INVALID; }
-    NttDomain d;
+    NttDomain planned;
+    planned.log2n = log2n;
     auto it = ctx->domains.find(log2n);
-    if (it != ctx->domains.end()) { // a built domain keeps the plan it was built with
-        d.passes = it->second.passes;
-        d.use_pass8 = it->second.use_pass8;
-        d.tile_log8 = it->second.tile_log8;
-        for (int q = 0; q < NTT_MAX_PASSES; q++) d.logR[q] = it->second.logR[q];
-    } else {
-        d.log2n = log2n;
-        plan_passes(ctx, d);
-    }
+    if (it == ctx->domains.end()) plan_passes(ctx, planned);
+    const NttDomain& d = it != ctx->domains.end() ? it->second : planned; // a built domain keeps the plan it was built with
+    constexpr int code[NTT_FAMILIES] = { 0, 8, 81, 29 };
     *passes = d.passes;
     for (int q = 0; q < NTT_MAX_PASSES; q++) log_radix[q] = q < d.passes ? d.logR[q] : 0;
     *tile_log = d.use_pass8 ? d.tile_log8 : ctx->ntt_tile_log;
-    if (!d.use_pass8) *kernel = 0;
-    else if (ctx->ntt_limbs29 == 1 || (ctx->ntt_limbs29 == -1 && NTT_LIMBS29_AUTO(log2n))) *kernel = 29;
-    else if (ctx->ntt_lds_planes == 1 || (ctx->ntt_lds_planes == 0 && log2n >= 22)) *kernel = 81;
-    else *kernel = 8;
+    *kernel = code[pass_family(ctx, d)];
     return BBG_OK;
 }
 
