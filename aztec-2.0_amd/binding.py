@@ -97,6 +97,10 @@ def load_library():
         "bbg_open_all": (cint, [vp, vp, vp]),
         "bbg_open_all_device_bytes": (cint, [vp, ctypes.POINTER(sz)]),
         "bbg_open_all_free": (None, [vp]),
+        "bbg_cells_values_device": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
+        "bbg_cells_values": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
+        "bbg_cells_recover_device": (cint, [vp, vp, sz, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
+        "bbg_cells_recover": (cint, [vp, vp, sz, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
         "bbg_ntt": (cint, [vp, vp, ctypes.c_uint, cint, sz, vp]),
         "bbg_coset_fft_extend": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp]),
         "bbg_quotient_widget_device": (cint, [vp, cint, vp, ctypes.c_uint, vp, vp, vp]),
@@ -183,6 +187,7 @@ EXPORTED_SYMBOLS = [
     "bbg_prover_evaluate_lagrange",
     "bbg_g1_ntt", "bbg_g1_ntt_device", "bbg_open_all_prepare", "bbg_open_all_device", "bbg_open_all", "bbg_open_all_device_bytes", "bbg_open_all_free",
     "bbg_open_all_prepare_cells", "bbg_open_all_count",
+    "bbg_cells_values_device", "bbg_cells_values", "bbg_cells_recover_device", "bbg_cells_recover",
 ]
 
 
@@ -471,6 +476,42 @@ class Bbg:
         else:
             self._ck(self.lib.bbg_open_all_prepare_cells(self.ctx, srs.handle, log2n, log2cell, ctypes.byref(h)))
         return OpenAll(self, h, log2n)
+
+    # ---- cells as data (csrc/cells.hip): n = 2^log2n, l = 2^log2cell, r = n / l, cell m = { w^(m + r t) : t < l }
+    def cells_values(self, coeffs, log2n, log2cell):
+        """The values of every cell of (count * n, 4) Montgomery coefficients, count polynomials one after the other: (count * n, 4)
+        canonical words, out[p n + m l + t] = f_p(w^(m + r t)) (bbg_cells_values)."""
+        c = _u64(coeffs, 4)
+        count, rest = divmod(c.shape[0], 1 << log2n)
+        if rest:
+            raise ValueError(f"expected a multiple of {1 << log2n} coefficients, got {c.shape[0]}")
+        out = np.zeros_like(c)
+        self._ck(self.lib.bbg_cells_values(self.ctx, c.ctypes.data, log2n, log2cell, count, out.ctypes.data))
+        return out
+
+    def cells_values_device(self, d_coeffs, log2n, log2cell, count, d_out):
+        """Device pointers, count x n values each, no overlap; asynchronous on the context stream (bbg_cells_values_device)."""
+        self._ck(self.lib.bbg_cells_values_device(self.ctx, ctypes.c_void_p(d_coeffs), log2n, log2cell, count, ctypes.c_void_p(d_out)))
+
+    def cells_recover(self, cell_ids, values, log2n, log2cell):
+        """The coefficients of the polynomials of degree < K l through the K cells cell_ids: values is (count * K * l, 4), cell k of
+        polynomial p at (p K + k) l; returns (count * n, 4) canonical words (bbg_cells_recover)."""
+        ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        v = _u64(values, 4)
+        per = max(ids.shape[0], 1) << log2cell
+        count, rest = divmod(v.shape[0], per)
+        if rest:
+            raise ValueError(f"expected a multiple of {per} values, got {v.shape[0]}")
+        out = np.zeros((count << log2n, 4), dtype=np.uint64)
+        self._ck(self.lib.bbg_cells_recover(self.ctx, ids.ctypes.data, ids.shape[0], v.ctypes.data, log2n, log2cell, count, out.ctypes.data))
+        return out
+
+    def cells_recover_device(self, cell_ids, d_values, log2n, log2cell, count, d_out_coeffs):
+        """Device pointers (count x K x l values in, count x n coefficients out, no overlap), cell_ids on the host; asynchronous
+        (bbg_cells_recover_device)."""
+        ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        self._ck(self.lib.bbg_cells_recover_device(self.ctx, ids.ctypes.data, ids.shape[0], ctypes.c_void_p(d_values), log2n, log2cell, count,
+                                                   ctypes.c_void_p(d_out_coeffs)))
 
     # ---- NTT
     def ntt(self, coeffs, op=FFT, generator_size=0, constant=None):

@@ -266,6 +266,8 @@ void bbg_destroy(bbg_ctx* ctx)
     ctx->msm.release();
     ctx->msm_tiny.release();
     msm_release_aux_streams(ctx);
+    if (ctx->cells_pinned) (void)hipHostFree(ctx->cells_pinned);
+    if (ctx->cells_copied) (void)hipEventDestroy(ctx->cells_copied);
     if (ctx->upload_stream) {
         (void)hipStreamDestroy(ctx->upload_stream);
         (void)hipEventDestroy(ctx->ev_upload_go);
@@ -938,6 +940,62 @@ void bbg_open_all_free(struct bbg_open_all* h)
     if (!h) return;
     (void)hipSetDevice(h->ctx->device);
     open_all_release(h);
+}
+
+// ------------------------------------------------------------------------------------------------ cells (cells.hip)
+int bbg_cells_values_device(bbg_ctx* ctx, const void* d_coeffs, unsigned log2n, unsigned log2cell, size_t count, void* d_out)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return cells_values(ctx, d_coeffs, log2n, log2cell, count, d_out, ctx->stream);
+}
+
+int bbg_cells_values(bbg_ctx* ctx, const uint64_t* coeffs, unsigned log2n, unsigned log2cell, size_t count, uint64_t* out)
+{
+    CHECK_CTX(ctx);
+    if (!coeffs || !out) { set_error("bbg_cells_values: null argument"); return BBG_E_INVALID; }
+    int rc = cells_check_shape("bbg_cells_values", log2n, log2cell, count);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t bytes = count * ((size_t)1 << log2n) * 32;
+    rc = ctx->staging.ensure(2 * bytes);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p; // coefficients | values
+    BBG_HIP(hipMemcpyAsync(st, coeffs, bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = cells_values(ctx, st, log2n, log2cell, count, st + bytes, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out, st + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
+int bbg_cells_recover_device(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* d_values, unsigned log2n, unsigned log2cell, size_t count,
+                             void* d_out_coeffs)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return cells_recover(ctx, cell_ids, K, d_values, log2n, log2cell, count, d_out_coeffs, ctx->stream);
+}
+
+int bbg_cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const uint64_t* values, unsigned log2n, unsigned log2cell, size_t count,
+                      uint64_t* out_coeffs)
+{
+    CHECK_CTX(ctx);
+    if (!values || !out_coeffs) { set_error("bbg_cells_recover: null argument"); return BBG_E_INVALID; }
+    int rc = cells_check_shape("bbg_cells_recover", log2n, log2cell, count);
+    if (rc == BBG_OK) rc = cells_check_ids("bbg_cells_recover", cell_ids, K, log2n, log2cell);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t in_bytes = count * K * ((size_t)32 << log2cell), out_bytes = count * ((size_t)32 << log2n);
+    rc = ctx->staging.ensure(in_bytes + out_bytes);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p; // coefficients | values
+    BBG_HIP(hipMemcpyAsync(st + out_bytes, values, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = cells_recover(ctx, cell_ids, K, st + out_bytes, log2n, log2cell, count, st, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out_coeffs, st, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
 }
 
 int bbg_srs_retain(bbg_srs* srs)

@@ -196,13 +196,19 @@ struct bbg_ctx {
     bbg::DevBuf ecntt_work;
     int batch_mul_glv = 1;           // option "batch_mul_glv": 1 = windowed GLV (xyzz_mul_glv), 0 = the bit-serial double-and-add (xyzz_mul_fr), A/B
     long batch_mul_lanes = 1L << 17; // option "batch_mul_lanes": lanes of the variable-base kernels = tables held (a multiple of 64; 2^17 = two waves per SIMD)
+    // cells.hip: the tables of one bbg_cells_recover call (roots, points, Z, slot map) or the working array of bbg_cells_values, and the pinned
+    // host array the slot map and id lists of a call are built in (cells_copied: the copy of the last call has read it)
+    bbg::DevBuf cells_work;
+    void* cells_pinned = nullptr;
+    size_t cells_pinned_bytes = 0;
+    hipEvent_t cells_copied = nullptr;
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
 };
 
 // every context buffer that bbg_memory_report counts under `scratch`: a new buffer is one member above plus one entry here
 constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::ntt_scratch, &bbg_ctx::staging,  &bbg_ctx::poly_scratch, &bbg_ctx::gp_totals,  &bbg_ctx::quot_setup,
-    &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,
+    &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,   &bbg_ctx::cells_work,
 };
 
 // bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle.
@@ -351,4 +357,13 @@ int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, u
 int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t stream);
 size_t open_all_bytes(unsigned log2n, unsigned log2cell);
 void open_all_release(struct bbg_open_all* h);
+// cells.hip.  The checks return BBG_E_INVALID with the error text set; `who` names the entry point in it.
+int cells_check_shape(const char* who, unsigned log2n, unsigned log2cell, size_t count);
+int cells_check_ids(const char* who, const uint32_t* cell_ids, size_t K, unsigned log2n, unsigned log2cell);
+// d_out[p n + m l + t] = f_p(w^(m + r t)), canonical, for `count` coefficient arrays at d_coeffs (read only, no overlap).  Queues only.
+int cells_values(bbg_ctx* ctx, const void* d_coeffs, unsigned log2n, unsigned log2cell, size_t count, void* d_out, hipStream_t stream);
+// d_out_coeffs[p n ..] = the interpolant of degree < K l through cells cell_ids[k] (HOST, read before the call returns) of polynomial p, whose
+// values lie at d_values + ((p K + k) l) x 32 B; canonical.  d_out_coeffs is also the working array of the three transforms.  Queues only.
+int cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* d_values, unsigned log2n, unsigned log2cell, size_t count,
+                  void* d_out_coeffs, hipStream_t stream);
 } // namespace bbg

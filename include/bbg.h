@@ -214,9 +214,9 @@ int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_
  * may be freed at once.  The handle holds l G1 transforms at 2r of the string's residue classes, and a call then runs G1 transforms at 2r
  * and r instead of 2n and n.  Its memory: 2n x 64 B of transformed points, 2n x 128 B of products, 2n x 32 B of scalars, 2r x 128 B +
  * r x 128 B of working arrays (bbg_open_all_device_bytes), outside bbg_memory_report like the all-points handle's.
- *   The VALUES of cell m are f(w_n^(m + r t)), t < l: bbg_ntt(BBG_FFT) of the n coefficients, read at index m with stride r.  This
- * library does not compute them here and does not verify: checking a cell proof pairs against [x^l]_2, a G2 point that this library
- * does not make. */
+ *   The VALUES of cell m are f(w_n^(m + r t)), t < l: bbg_ntt(BBG_FFT) of the n coefficients, read at index m with stride r.
+ * bbg_cells_values writes them cell by cell, and bbg_cells_recover gives the coefficients back from any K of the r cells (below).  This
+ * library does not verify: checking a cell proof pairs against [x^l]_2, a G2 point that this library does not make. */
 int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
 /* The number of proofs a call writes: n >> log2cell (n for a handle of bbg_open_all_prepare). */
 int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs);
@@ -229,6 +229,32 @@ int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs);
 int bbg_open_all_device(struct bbg_open_all* h, const void* d_coeffs, void* d_out_affine);
 /* Host arrays; returns when the proofs are in out_affine. */
 int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_affine);
+
+/* ---- cells as data: the values of every cell of a polynomial, and the polynomial back from a subset of its cells (erasure decoding; the
+ *      consumer side of the cell handle above, pure Fr work).  n = 2^log2n, l = 2^log2cell, r = n / l, cell m < r = { w_n^(m + r t) : t < l }.
+ *      Shared by all four: Montgomery Fr, every input any representative in [0, 2r_mod), every output canonical; 1 <= log2n <= 28,
+ *      0 <= log2cell <= log2n - 1, 1 <= count <= 32 polynomials per call, laid out one after the other.  A null pointer, a value out of
+ *      range or an overlap of input and output is BBG_E_INVALID: nothing is queued and the output stays untouched.  The device entries
+ *      queue on the context stream and do not synchronise the host once the working memory (`scratch` in bbg_memory_report, released by
+ *      bbg_memory_trim) and the domain's tables have their size.  Timed under "cells_gather" (values), "cells_z", "cells_scatter",
+ *      "cells_divide", "cells_canon" (recovery), beside "ntt_pass" and "fr_batch_invert". ---- */
+/* d_out[p n + m l + t] = f_p(w_n^(m + r t)): cell-major, cell m contiguous.  d_coeffs: count x n coefficients, read only; d_out: count x n
+ * values, no overlap with d_coeffs.  One forward transform per polynomial, then a transposition. */
+int bbg_cells_values_device(bbg_ctx* ctx, const void* d_coeffs, unsigned log2n, unsigned log2cell, size_t count, void* d_out);
+/* Host-buffer form: upload, compute, download; synchronous. */
+int bbg_cells_values(bbg_ctx* ctx, const uint64_t* coeffs, unsigned log2n, unsigned log2cell, size_t count, uint64_t* out);
+/* The unique polynomial of degree < K l through K cells.  cell_ids: HOST array of K distinct cell indices below r, 1 <= K <= r, in any
+ * order, read before the call returns; every polynomial of the call has the same cells.  d_values: count x K x l values, cell k of
+ * polynomial p at (p K + k) l in bbg_cells_values' order within the cell.  d_out_coeffs: count x n coefficients, no overlap with d_values;
+ * coefficients K l .. n - 1 are exactly zero.  There is no 50 % rule: a caller whose polynomial has degree < n / 2 passes any K >= r / 2
+ * cells and gets it back; values that lie on no polynomial of the caller's degree bound show as non-zero coefficients above that bound.
+ * Cost: three Fr transforms at n per polynomial and, once per call, 2 r products of r - K factors (log2cell = 0, interpolation from
+ * single points, is legal and quadratic in the number of missing points). */
+int bbg_cells_recover_device(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* d_values, unsigned log2n, unsigned log2cell, size_t count,
+                             void* d_out_coeffs);
+/* Host-buffer form: upload, compute, download; synchronous. */
+int bbg_cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const uint64_t* values, unsigned log2n, unsigned log2cell, size_t count,
+                      uint64_t* out_coeffs);
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes);
 /* Releases the handle and its device memory (a device synchronisation); must precede bbg_destroy of its context. */
 void bbg_open_all_free(struct bbg_open_all* h);
@@ -493,7 +519,7 @@ typedef struct bbg_memory_info {
     size_t ntt_tables;     /* per-domain twiddle / coset tables (5 x 32n bytes per prepared size) */
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
     size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
-                              variable-base lanes' tables, the working set of bbg_g1_ntt */
+                              variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
@@ -545,7 +571,8 @@ int bbg_memory_trim(bbg_ctx* ctx, int tables, size_t* released);
 int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
  * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul",
- * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum".  enable(…, 1) clears previous samples. */
+ * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum",
+ * "cells_gather", "cells_z", "cells_scatter", "cells_divide", "cells_canon".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
