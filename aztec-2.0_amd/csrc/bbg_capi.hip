@@ -1446,4 +1446,32 @@ int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint6
     return BBG_OK;
 }
 
+int bbg_limb29_op_shape(int which, int op, int* operands, int* results)
+{
+    if (!operands || !results) { set_error("bbg_limb29_op_shape: null argument"); return BBG_E_INVALID; }
+    const int rc = limb29_op_shape(which, op, operands, results);
+    if (rc) set_error("bbg_limb29_op_shape: unknown (which, op)");
+    return rc;
+}
+int bbg_limb29_op(bbg_ctx* ctx, int which, int op, const uint32_t* in, size_t n, uint32_t* out)
+{
+    CHECK_CTX(ctx);
+    int operands = 0, results = 0;
+    if (limb29_op_shape(which, op, &operands, &results)) { set_error("bbg_limb29_op: unknown (which, op)"); return BBG_E_INVALID; }
+    if (n > ((size_t)1 << 20)) { set_error("bbg_limb29_op: n > 2^20"); return BBG_E_INVALID; }
+    if (n == 0) return BBG_OK;
+    if (!in || !out) { set_error("bbg_limb29_op: null argument"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t in_bytes = n * operands * 36, out_bytes = n * results * 36; // rows of 9 words
+    int rc = ctx->staging.ensure(in_bytes + out_bytes);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p;
+    BBG_HIP(hipMemcpyAsync(st, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = limb29_op_device(which, op, st, st + in_bytes, n, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out, st + in_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
 } // extern "C"

@@ -315,6 +315,9 @@ int ntt_root_pow(bbg_ctx* ctx, unsigned log2n, uint64_t e, int inverse, uint64_t
 int ntt_fr_pow(bbg_ctx* ctx, const uint64_t* base, uint64_t e, uint64_t* out, hipStream_t stream);
 int ntt_cross_dft(bbg_ctx* ctx, const void* d_in, void* d_out, unsigned log2G, size_t len, unsigned log2n, int inverse, hipStream_t stream);
 int field_op_device(int which, int op, const void* a, const void* b, void* out, size_t n, hipStream_t stream);
+// limb29_check.hip: the conformance kernels of the 29-bit-limb arithmetic (bbg_limb29_op)
+int limb29_op_shape(int which, int op, int* operands, int* results);
+int limb29_op_device(int which, int op, const void* d_in, void* d_out, size_t n, hipStream_t stream);
 // h_scalars (optional): the n scalars are still on the HOST and d_scalars is where they belong on the device -- msm_run uploads them
 // itself, piece by piece, overlapped with its first pass
 int msm_run(bbg_ctx* ctx, Srs& srs, const void* d_scalars, size_t from, size_t n, void* d_out_jac,

@@ -580,6 +580,16 @@ int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* la
  * 6/7 mul / CIOS mul without pre-reduction, 8 a*a - b*b and 9 (-a)(-b) - a(-b) through the fused two-product multiplier,
  * 10 / 11 the inverse of a (0 -> 0) by the binary extended Euclid of the set-up kernels, per lane / on the scalar unit (one wave per element). */
 int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+/* Self test entry of the 29-bit-limb arithmetic, used by tests (like bbg_field_op, but on RAW operands: nothing is pre-reduced, so a lazily
+ * reduced value -- limbs above 29 bits, a value of many p -- reaches the device primitive as it is, and the raw result limbs come back).
+ * which: 0 Fr, 1 Fq.  in: n vectors of `operands` rows, out: n vectors of `results` rows (bbg_limb29_op_shape gives both counts, without
+ * device work).  A row is 9 uint32_t: a limb value uses all nine; an 8 x u32 field element uses words 0..7 and word 8 is written as 0.
+ * op: one primitive of csrc/field29.hip.h, field29c.hip.h, curve29.hip.h, ntt29.hip.h or w29.hip.h each; the numbers are listed in
+ * csrc/limb29_check.hip (BBG_L29_OPS; 100 + i / 200 + i / 300 + i: f29_sub / f29_neg / n29_bfly with the i-th (M, E) pair of BBG_L29_PAIRS).
+ * The device checks no precondition: a vector outside an op's contract gives wrapped arithmetic.
+ * BBG_E_INVALID (out untouched) for an unknown (which, op), a null pointer with n > 0, or n > 2^20; n = 0 is BBG_OK. */
+int bbg_limb29_op(bbg_ctx* ctx, int which, int op, const uint32_t* in, size_t n, uint32_t* out);
+int bbg_limb29_op_shape(int which, int op, int* operands, int* results);
 
 #ifdef __cplusplus
 }
