@@ -939,7 +939,8 @@ def test_poly_linear_combination_every_term_count(pkg, oracle, bbg, limbs29):
     """The 29-bit linear combination sums four terms per reduction with a tail of one to three (poly29.hip.h; option poly_limbs29, 0 = the
     32-bit kernel): every tail length, the 32-term maximum, with and without a base, over inputs that include the largest canonical value
     p - 1 and COARSE residues p + x (a device array may hold any representative below 2p) -- against the oracle's field operations.  The
-    evaluations (one and several polynomials) run under the same option at ragged lengths."""
+    evaluation of ONE polynomial (bbg_poly_evaluate_device) runs under the same option at ragged lengths; the several-polynomial kernels
+    (k_multi_eval_partial / k_multi_eval_partial29) are reached only through a prover handle: tests/test_gpu_prover_rounds.py, both option values."""
     import torch
     P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
     n = 777
