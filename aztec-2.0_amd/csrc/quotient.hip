@@ -16,6 +16,7 @@
 #include "bbg_internal.h"
 
 #include <cstring>
+#include <initializer_list>
 #include "field.hip.h"
 #include "ntt_consts.hip.h"
 
@@ -26,7 +27,11 @@ enum { QP_W1 = 0, QP_W2, QP_W3, QP_W4, QP_Z, QP_S1, QP_S2, QP_S3, QP_S4, QP_Q1, 
        QP_QMIMC_C = QP_COUNT, QP_QMIMC_S, QP_EXT_COUNT }; // the MiMC widget's two selectors: the extended table (bbg.h)
 static_assert(QP_COUNT == BBG_QP_COUNT && QP_EXT_COUNT == BBG_QP_EXT_COUNT && QP_QMIMC_C == BBG_QP_EXT_Q_MIMC_COEFFICIENT,
               "include/bbg.h and quotient.hip disagree on the polynomial table");
-constexpr int WIDGET_COUNT = 8;
+constexpr int WIDGET_COUNT = BBG_WIDGET_MIMC + 1;
+// What a widget hands on to the next one of its round, in four bits: its relation count r, for alpha_next = alpha_base * alpha^r (update_alpha,
+// transition_widget.hpp:88-94: alpha_powers[num_independent_relations - 1] * alpha), or HAND_ON_FOURTH for a widget that assigns the quotient:
+// alpha_next = alpha_base^4 (permutation_widget_impl.hpp:419).  The widget table below is where each widget's value comes from.
+constexpr uint32_t HAND_ON_FOURTH = 15;
 
 struct QuotientSetup {
     Fr ap[7];       // alpha_base * alpha^k
@@ -36,7 +41,7 @@ struct QuotientSetup {
     Fr beta_g;      // beta * g (g = the small domain's coset generator): beta*g*w^i is the identity-permutation term
     Fr k1, k2, k3;  // coset generators of the wire columns 2..4 (fr::coset_generator(0..2))
     Fr one, c2, c3, c6, c7, c17, c81, c83;
-    Fr alpha_out[WIDGET_COUNT]; // per widget: the alpha_base the next widget starts from
+    Fr alpha_next;  // the alpha_base the next widget of the round starts from (last: the kernels read none of it)
 };
 struct QuotientArgs {
     const Fr* p[QP_EXT_COUNT];
@@ -54,14 +59,14 @@ __device__ __forceinline__ Fr fr_small(uint32_t k) // the Montgomery residue of 
 }
 // challenges arrive as Montgomery limbs from the host, BY VALUE as a kernel argument (no pageable-memory copy whose source the
 // caller could reuse before it ran); everything derived from them is computed here (the product has no CPU field arithmetic).
-// alpha_base_dev (optional): take alpha_base from device memory instead -- the alpha_out of the previous widget's set-up block,
-// which chains the widgets of a round without a host round trip.
 struct QuotientChallenges {
     Fr v[9]; // alpha_base, alpha, beta, gamma, delta, g, k1, k2, k3
 };
+// One set-up block on one lane; returns its alpha_next.  hand_on: the block's widget, as above.
 // consts: a block of the same launch whose challenge-independent constants and alpha powers are already there (the chain kernel fills
 // them once and copies: 17 products per further block instead of 30)
-__device__ __forceinline__ void quotient_setup_one(QuotientSetup* s, const QuotientChallenges& in, const Fr& alpha_base, const QuotientSetup* consts = nullptr)
+__device__ __forceinline__ Fr quotient_setup_one(QuotientSetup* s, const QuotientChallenges& in, const Fr& alpha_base, uint32_t hand_on,
+                                                 const QuotientSetup* consts = nullptr)
 {
     const Fr alpha = in.v[1];
     s->alpha = alpha;
@@ -81,12 +86,15 @@ __device__ __forceinline__ void quotient_setup_one(QuotientSetup* s, const Quoti
     s->k1 = in.v[6];
     s->k2 = in.v[7];
     s->k3 = in.v[8];
-    Fr a = alpha_base;
-    for (int k = 0; k < 7; k++) {
+    Fr a = alpha_base, next = alpha_base;
+    for (uint32_t k = 0; k < 7; k++) {
         s->ap[k] = a;
         a = fe_mul(a, alpha);
+        if (k + 1 == hand_on) next = a;
     }
     s->alpha_base_sqr = fe_sqr(alpha_base);
+    if (hand_on == HAND_ON_FOURTH) next = fe_sqr(s->alpha_base_sqr);
+    s->alpha_next = next;
     s->one = Fr::one();
     if (consts) {
         s->c2 = consts->c2; s->c3 = consts->c3; s->c6 = consts->c6; s->c7 = consts->c7;
@@ -100,35 +108,24 @@ __device__ __forceinline__ void quotient_setup_one(QuotientSetup* s, const Quoti
         s->c81 = fr_small(81);
         s->c83 = fr_small(83);
     }
-    // update_alpha (transition_widget.hpp:88-94): alpha_powers[num_independent_relations - 1] * alpha
-    s->alpha_out[0] = fe_sqr(s->alpha_base_sqr);     // permutation: alpha_base^4 (permutation_widget_impl.hpp:419)
-    s->alpha_out[1] = fe_mul(s->ap[1], alpha);       // arithmetic: 2 relations
-    s->alpha_out[2] = fe_mul(s->ap[6], alpha);       // fixed base: 7
-    s->alpha_out[3] = fe_mul(s->ap[3], alpha);       // range: 4
-    s->alpha_out[4] = fe_mul(s->ap[3], alpha);       // logic: 4
-    s->alpha_out[5] = s->alpha_out[0];               // permutation, 3 wires
-    s->alpha_out[6] = s->ap[1];                      // standard arithmetic: 1 relation
-    s->alpha_out[7] = s->ap[2];                      // MiMC: 2 relations
+    return next;
 }
-__global__ void k_quotient_setup(QuotientSetup* s, QuotientChallenges in, const Fr* alpha_base_dev)
+// The set-up blocks of a whole widget chain in ONE launch, on one lane: block w starts from the alpha_next of block w - 1 (r4: a launch per
+// widget was a chain of five 31-us single-lane kernels, 0.16 ms of every proof).  hand_on: 4 bits per block, as in WidgetPlan.
+__global__ void k_quotient_setup_chain(QuotientSetup* setups, QuotientChallenges in, int count, uint32_t hand_on)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    quotient_setup_one(s, in, alpha_base_dev ? fe_load<FrP>(alpha_base_dev) : in.v[0]);
+    Fr alpha_base = in.v[0];
+    for (int w = 0; w < count; w++) alpha_base = quotient_setup_one(setups + w, in, alpha_base, (hand_on >> (4 * w)) & 15, w ? setups : nullptr);
 }
-// The set-up blocks of a whole widget chain in ONE launch: block w starts from the alpha_out block w - 1 produced for its widget (r4: a
-// launch per widget was a chain of five 31-us single-lane kernels, 0.16 ms of every proof).
-struct WidgetChain {
-    int count;
-    int widget[8];
-};
 // The same blocks with the lanes of one wave working side by side (r5).  Every value of the chain is alpha_base^(4^j) * alpha^e with (j, e)
-// known to the HOST from the widget list alone -- a permutation widget hands on base^4, the others base * alpha^r (update_alpha,
-// transition_widget.hpp:88-94) -- so block w's eight powers base_w * alpha^k are eight independent lanes: a shared table alpha^(2^b), one
-// power from it, one product.  The serial kernel above is a chain of ~ 90 dependent products on one lane (59 us: 3 % of a 2^12-gate proof);
-// here the longest chain is the table's squarings + one lane's power + two squarings: ~ 14 products.
+// known to the HOST from the widget list alone -- a widget that assigns hands on base^4, the others base * alpha^r -- so block w's eight
+// powers base_w * alpha^k are eight independent lanes: a shared table alpha^(2^b), one power from it, one product.  The serial kernel above is
+// a chain of ~ 90 dependent products on one lane (59 us: 3 % of a 2^12-gate proof); here the longest chain is the table's squarings + one lane's
+// power + two squarings: ~ 14 products.
 struct WidgetPlan {
     int count;
-    uint32_t widgets; // 4 bits per block: the widget
+    uint32_t hand_on; // 4 bits per block: the relation count of the block's widget, or HAND_ON_FOURTH
     uint32_t c4;      // 4 bits per block: j, the block's base is alpha_base^(4^j) * alpha^e
     uint64_t e[2];    // 16 bits per block: e
     int table_bits;   // alpha^(2^b) for b < table_bits (>= 2) covers every e + 7
@@ -158,27 +155,24 @@ __global__ void __launch_bounds__(64) k_quotient_setup_plan(QuotientSetup* setup
     if (w >= plan.count) return;
     QuotientSetup* s = setups + w;
     const uint32_t e = (uint32_t)((w < 4 ? plan.e[0] >> (16 * w) : plan.e[1] >> (16 * (w - 4))) & 0xffff);
+    const uint32_t hand_on = (plan.hand_on >> (4 * w)) & 15;
     const Fr v = fe_mul(C[(plan.c4 >> (4 * w)) & 15], pow_from_table(T, (uint64_t)(e + k))); // base_w * alpha^k
     if (k < 7) s->ap[k] = v;
-    switch (k) {
+    if ((uint32_t)k == hand_on) s->alpha_next = v; // a relation count is 1 .. 7
+    switch (k) { // the block's other members, shared out among its lanes
     case 0: {
         const Fr sq = fe_sqr(v);
         s->alpha_base_sqr = sq;
-        const Fr q = fe_sqr(sq); // permutation: alpha_base^4 (permutation_widget_impl.hpp:419)
-        s->alpha_out[0] = q;
-        s->alpha_out[5] = q;
+        if (hand_on == HAND_ON_FOURTH) s->alpha_next = fe_sqr(sq);
         break;
     }
     case 1: {
-        s->alpha_out[6] = v; // standard arithmetic: 1 relation
         s->alpha2 = T[1];
         const Fr a3 = fe_mul(T[1], alpha);
         s->alpha3x2 = fe_add(a3, a3);
         break;
     }
     case 2:
-        s->alpha_out[1] = v; // arithmetic: 2 relations
-        s->alpha_out[7] = v; // MiMC: 2
         s->beta_g = fe_mul(in.v[2], in.v[5]);
         break;
     case 3:
@@ -186,10 +180,6 @@ __global__ void __launch_bounds__(64) k_quotient_setup_plan(QuotientSetup* setup
         s->beta = in.v[2];
         s->gamma = in.v[3];
         s->delta = in.v[4];
-        break;
-    case 4:
-        s->alpha_out[3] = v; // range: 4 relations
-        s->alpha_out[4] = v; // logic: 4
         break;
     case 5:
         s->k1 = in.v[6];
@@ -206,43 +196,6 @@ __global__ void __launch_bounds__(64) k_quotient_setup_plan(QuotientSetup* setup
         s->c81 = fr_small(81);
         s->c83 = fr_small(83);
         break;
-    default:
-        s->alpha_out[2] = v; // fixed base: 7 relations
-        break;
-    }
-}
-// (j, e) of every block of a widget list; false when a value leaves the plan's fields (the serial kernel then)
-static bool widget_plan(const int* widgets, int count, WidgetPlan& plan)
-{
-    static const int RELATIONS[WIDGET_COUNT] = { 0, 2, 7, 4, 4, 0, 1, 2 }; // alpha_out = base * alpha^r; widgets 0 and 5 hand on base^4
-    memset(&plan, 0, sizeof(plan));
-    plan.count = count;
-    uint64_t e = 0;
-    int j = 0, bits = 2;
-    for (int w = 0; w < count; w++) {
-        if (j > PLAN_MAX_C4 || e + 7 >= ((uint64_t)1 << PLAN_MAX_BITS)) return false;
-        plan.widgets |= (uint32_t)widgets[w] << (4 * w);
-        plan.c4 |= (uint32_t)j << (4 * w);
-        plan.e[w >> 2] |= e << (16 * (w & 3));
-        while ((e + 7) >> bits) bits++;
-        if (j > plan.max_c4) plan.max_c4 = j;
-        if (widgets[w] == 0 || widgets[w] == 5) {
-            j++;
-            e *= 4;
-        } else {
-            e += (uint64_t)RELATIONS[widgets[w]];
-        }
-    }
-    plan.table_bits = bits;
-    return count <= 8;
-}
-__global__ void k_quotient_setup_chain(QuotientSetup* setups, QuotientChallenges in, WidgetChain chain)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Fr alpha_base = in.v[0];
-    for (int w = 0; w < chain.count; w++) {
-        quotient_setup_one(setups + w, in, alpha_base, w ? setups : nullptr);
-        alpha_base = setups[w].alpha_out[chain.widget[w]];
     }
 }
 
@@ -333,35 +286,6 @@ __global__ void __launch_bounds__(256) k_quotient_mimc(QuotientArgs a)
     fe_store<FrP>(a.quotient + i, fe_add(q, fe_mul(id, QLOAD(QP_QMIMC_S, i))));
 }
 
-// ---- turbo arithmetic gate:
-//   alpha_base * [ q_arith (q_m w1 w2 + q_1 w1 + q_2 w2 + q_3 w3 + q_4 w4 + q_c) + alpha q_5 q_arith w4 (w4 - 1)(w4 - 2) ]
-//   + alpha_base (q_arith^2 - q_arith) d (9 d - 2 d^2 - 7),   d = w3 - 4 w4   (high-bit extraction, active when q_arith = 2)
-__global__ void __launch_bounds__(256) k_quotient_turbo_arith(QuotientArgs a)
-{
-    const QuotientSetup& s = *a.s;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > a.mask) return;
-    const Fr w1 = QLOAD(QP_W1, i), w2 = QLOAD(QP_W2, i), w3 = QLOAD(QP_W3, i), w4 = QLOAD(QP_W4, i);
-    const Fr qa = QLOAD(QP_QARITH, i);
-    Fr gate = fe_mul(fe_mul(w1, w2), QLOAD(QP_QM, i));
-    gate = fe_add(gate, fe_mul(w1, QLOAD(QP_Q1, i)));
-    gate = fe_add(gate, fe_mul(w2, QLOAD(QP_Q2, i)));
-    gate = fe_add(gate, fe_mul(w3, QLOAD(QP_Q3, i)));
-    gate = fe_add(gate, fe_mul(w4, QLOAD(QP_Q4, i)));
-    gate = fe_add(gate, QLOAD(QP_QC, i));
-    Fr t = fe_mul(fe_sub(fe_sqr(w4), w4), fe_sub(w4, s.c2));
-    t = fe_mul(fe_mul(t, s.alpha), QLOAD(QP_Q5, i));
-    gate = fe_mul(fe_add(gate, t), qa);
-    const Fr d = fe_sub(w3, x4(w4));
-    const Fr d2 = fe_sqr(d);
-    Fr h = fe_add(x4(d), x4(d));          // 8 d
-    h = fe_sub(fe_add(h, d), fe_add(d2, d2)); // 9 d - 2 d^2
-    h = fe_mul(fe_sub(h, s.c7), d);
-    h = fe_mul(h, fe_sub(fe_sqr(qa), qa));
-    const Fr q = fe_load<FrP>(a.quotient + i);
-    fe_store<FrP>(a.quotient + i, fe_add(q, fe_mul(fe_add(gate, h), s.ap[0])));
-}
-
 // ---- fixed-base scalar multiplication ladder over Grumpkin (y^2 = x^3 - 17); ap[k] = alpha_base alpha^k.  Two kernels -- the
 // selector-weighted terms and the gate identities -- because one kernel holding 8 wire values, 8 selectors and 7 alpha
 // powers needs 250 VGPRs (2 waves per SIMD, 5.0 ms at 4n = 2^22); split, each half re-reads the wires and stays near 128.
@@ -431,37 +355,53 @@ __global__ void __launch_bounds__(256) k_quotient_turbo_fixed_base_gate(Quotient
     fe_store<FrP>(a.quotient + i, fe_add(q, fe_mul(gate, qe)));
 }
 
+// ---- The three cheapest transition widgets: one body per identity, on wires the kernel below has loaded.  Each returns its widget's whole
+// contribution, which the kernel adds to the quotient; s is the widget's own set-up block (quotient29.hip.h has the same three parts).
+// ---- turbo arithmetic gate:
+//   alpha_base * [ q_arith (q_m w1 w2 + q_1 w1 + q_2 w2 + q_3 w3 + q_4 w4 + q_c) + alpha q_5 q_arith w4 (w4 - 1)(w4 - 2) ]
+//   + alpha_base (q_arith^2 - q_arith) d (9 d - 2 d^2 - 7),   d = w3 - 4 w4   (high-bit extraction, active when q_arith = 2)
+__device__ __forceinline__ Fr arith_part(const QuotientArgs& a, const QuotientSetup& s, uint32_t i, const Fr& w1, const Fr& w2, const Fr& w3,
+                                         const Fr& w4, const Fr& qc)
+{
+    const Fr qa = QLOAD(QP_QARITH, i);
+    Fr gate = fe_mul(fe_mul(w1, w2), QLOAD(QP_QM, i));
+    gate = fe_add(gate, fe_mul(w1, QLOAD(QP_Q1, i)));
+    gate = fe_add(gate, fe_mul(w2, QLOAD(QP_Q2, i)));
+    gate = fe_add(gate, fe_mul(w3, QLOAD(QP_Q3, i)));
+    gate = fe_add(gate, fe_mul(w4, QLOAD(QP_Q4, i)));
+    gate = fe_add(gate, qc);
+    Fr t = fe_mul(fe_sub(fe_sqr(w4), w4), fe_sub(w4, s.c2));
+    t = fe_mul(fe_mul(t, s.alpha), QLOAD(QP_Q5, i));
+    gate = fe_mul(fe_add(gate, t), qa);
+    const Fr d = fe_sub(w3, x4(w4));
+    const Fr d2 = fe_sqr(d);
+    Fr h = fe_add(x4(d), x4(d));          // 8 d
+    h = fe_sub(fe_add(h, d), fe_add(d2, d2)); // 9 d - 2 d^2
+    h = fe_mul(fe_sub(h, s.c7), d);
+    h = fe_mul(h, fe_sub(fe_sqr(qa), qa));
+    return fe_mul(fe_add(gate, h), s.ap[0]);
+}
 // ---- base-4 range check ("raster scan" over the 4 wire columns and the next row's 4th column):
 //   q_range * sum_k ap[k] f(D_k),  f(D) = D (D-1)(D-2)(D-3),  D_1 = w3 - 4 w4, D_2 = w2 - 4 w3, D_3 = w1 - 4 w2, D_4 = w4' - 4 w1
-__global__ void __launch_bounds__(256) k_quotient_turbo_range(QuotientArgs a)
+__device__ __forceinline__ Fr range_part(const QuotientArgs& a, const QuotientSetup& s, uint32_t i, const Fr& w1, const Fr& w2, const Fr& w3,
+                                         const Fr& w4, const Fr& w4n)
 {
-    const QuotientSetup& s = *a.s;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > a.mask) return;
-    const Fr w1 = QLOAD(QP_W1, i), w2 = QLOAD(QP_W2, i), w3 = QLOAD(QP_W3, i), w4 = QLOAD(QP_W4, i);
-    const Fr w4n = QLOAD(QP_W4, (i + 4) & a.mask);
     Fr sum = fe_mul(quad_check(fe_sub(w3, x4(w4)), s), s.ap[0]);
     sum = fe_add(sum, fe_mul(quad_check(fe_sub(w2, x4(w3)), s), s.ap[1]));
     sum = fe_add(sum, fe_mul(quad_check(fe_sub(w1, x4(w2)), s), s.ap[2]));
     sum = fe_add(sum, fe_mul(quad_check(fe_sub(w4n, x4(w1)), s), s.ap[3]));
-    const Fr q = fe_load<FrP>(a.quotient + i);
-    fe_store<FrP>(a.quotient + i, fe_add(q, fe_mul(sum, QLOAD(QP_QRANGE, i))));
+    return fe_mul(sum, QLOAD(QP_QRANGE, i));
 }
-
 // ---- AND / XOR on base-4 quads a, b (c = the output quad, w3 = a*b):
 //   q_logic alpha_base [ ((2 (a b - w3) alpha + f(a)) alpha + f(b)) alpha + 3 (a + b + c) - 2 E + q_c (9 c - 3 (a + b)) ]
 //   E = w3 ( w3 (4 w3 - 18 (a + b) + 81) + 18 (a^2 + b^2) - 81 (a + b) + 83 )
 //   a = w1' - 4 w1, b = w2' - 4 w2, c = w4' - 4 w4
-__global__ void __launch_bounds__(256) k_quotient_turbo_logic(QuotientArgs a)
+__device__ __forceinline__ Fr logic_part(const QuotientArgs& a, const QuotientSetup& s, uint32_t i, uint32_t ish, const Fr& w1, const Fr& w2,
+                                         const Fr& w3, const Fr& w4, const Fr& w4n, const Fr& qc)
 {
-    const QuotientSetup& s = *a.s;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > a.mask) return;
-    const uint32_t ish = (i + 4) & a.mask;
-    const Fr w3 = QLOAD(QP_W3, i);
-    const Fr qa = fe_sub(QLOAD(QP_W1, ish), x4(QLOAD(QP_W1, i)));
-    const Fr qb = fe_sub(QLOAD(QP_W2, ish), x4(QLOAD(QP_W2, i)));
-    const Fr qcq = fe_sub(QLOAD(QP_W4, ish), x4(QLOAD(QP_W4, i)));
+    const Fr qa = fe_sub(QLOAD(QP_W1, ish), x4(w1));
+    const Fr qb = fe_sub(QLOAD(QP_W2, ish), x4(w2));
+    const Fr qcq = fe_sub(w4n, x4(w4));
     const Fr sum = fe_add(qa, qb);
     Fr id = fe_sub(fe_mul(qa, qb), w3);
     id = fe_mul(fe_add(id, id), s.alpha);
@@ -480,80 +420,41 @@ __global__ void __launch_bounds__(256) k_quotient_turbo_logic(QuotientArgs a)
     e = fe_mul(e, w3);
     const Fr c3 = fe_add(fe_add(qcq, qcq), qcq), c9 = fe_add(fe_add(c3, c3), c3);
     Fr tail = fe_sub(fe_add(c3, sum3), fe_add(e, e));
-    tail = fe_add(tail, fe_mul(fe_sub(c9, sum3), QLOAD(QP_QC, i)));
+    tail = fe_add(tail, fe_mul(fe_sub(c9, sum3), qc));
     id = fe_mul(fe_add(id, tail), s.ap[0]);
-    const Fr q = fe_load<FrP>(a.quotient + i);
-    fe_store<FrP>(a.quotient + i, fe_add(q, fe_mul(id, QLOAD(QP_QLOGIC, i))));
+    return fe_mul(id, QLOAD(QP_QLOGIC, i));
 }
 
-// ---- arithmetic + range + logic in ONE pass over the wires (TurboPLONK round 4): the three cheapest transition widgets are memory-bound
-// on their own (each reads the four wire columns -- range and logic the shifted rows as well -- and read-modify-writes the quotient:
-// 0.57 + 0.66 + 0.64 ms at 4n = 2^22, profiles/r02_prover_kernel_stats_v3.txt); fused, the wires, their shifted rows, q_c and the
-// quotient are touched once.  Same identities, same alpha powers: each part takes its own set-up block (the alpha_base chain of
-// execute_fourth_round, prover.cpp:304-319, runs over the set-up kernels only), and field addition does not care about the order.
-__global__ void __launch_bounds__(256) k_quotient_turbo_arith_range_logic(QuotientArgs a, const QuotientSetup* s_range, const QuotientSetup* s_logic)
+// PARTS = 1 / 2 / 4: the arithmetic, range or logic widget alone (a.s = its set-up block).  PARTS = 7: the three in ONE pass over the wires
+// (TurboPLONK round 4).  Each is memory-bound on its own (it reads the four wire columns -- range and logic the shifted rows as well -- and
+// read-modify-writes the quotient: 0.57 + 0.66 + 0.64 ms at 4n = 2^22, profiles/r02_prover_kernel_stats_v3.txt); fused, the wires, their
+// shifted rows, q_c and the quotient are touched once.  Each part takes its own set-up block (a.s = the arithmetic widget's; the alpha_base
+// chain of execute_fourth_round, prover.cpp:304-319, runs over the set-up kernels only).  + on [0, 2p) words is addition in Z/2pZ, so
+// q + (a + r + l) here and ((q + a) + r) + l of three separate launches store the same words.
+// Waves per SIMD: 6 (at most 80 VGPRs) for the arithmetic widget alone, which the register allocator otherwise misses by two registers; 4 and
+// 3 are what the others reach unasked (scripts/isa_stats.py; profiles/quotient_refactor_isa.txt).
+template <int PARTS> __global__ void __launch_bounds__(256, PARTS == 1 ? 6 : PARTS == 7 ? 3 : 4)
+k_quotient_turbo_arith_range_logic(QuotientArgs a, const QuotientSetup* s_range, const QuotientSetup* s_logic)
 {
-    const QuotientSetup& s = *a.s; // arithmetic widget's block; alpha and the small constants are the same in all three
+    static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4 || PARTS == 7, "one widget, or all three");
+    const QuotientSetup& s = *a.s;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i > a.mask) return;
     const uint32_t ish = (i + 4) & a.mask;
     const Fr w1 = QLOAD(QP_W1, i), w2 = QLOAD(QP_W2, i), w3 = QLOAD(QP_W3, i), w4 = QLOAD(QP_W4, i);
-    const Fr w4n = QLOAD(QP_W4, ish);
-    const Fr qc = QLOAD(QP_QC, i);
     Fr total;
-    { // arithmetic (k_quotient_turbo_arith)
-        const Fr qa = QLOAD(QP_QARITH, i);
-        Fr gate = fe_mul(fe_mul(w1, w2), QLOAD(QP_QM, i));
-        gate = fe_add(gate, fe_mul(w1, QLOAD(QP_Q1, i)));
-        gate = fe_add(gate, fe_mul(w2, QLOAD(QP_Q2, i)));
-        gate = fe_add(gate, fe_mul(w3, QLOAD(QP_Q3, i)));
-        gate = fe_add(gate, fe_mul(w4, QLOAD(QP_Q4, i)));
-        gate = fe_add(gate, qc);
-        Fr t = fe_mul(fe_sub(fe_sqr(w4), w4), fe_sub(w4, s.c2));
-        t = fe_mul(fe_mul(t, s.alpha), QLOAD(QP_Q5, i));
-        gate = fe_mul(fe_add(gate, t), qa);
-        const Fr d = fe_sub(w3, x4(w4));
-        const Fr d2 = fe_sqr(d);
-        Fr h = fe_add(x4(d), x4(d));
-        h = fe_sub(fe_add(h, d), fe_add(d2, d2));
-        h = fe_mul(fe_sub(h, s.c7), d);
-        h = fe_mul(h, fe_sub(fe_sqr(qa), qa));
-        total = fe_mul(fe_add(gate, h), s.ap[0]);
-    }
-    { // range (k_quotient_turbo_range)
-        const QuotientSetup& r = *s_range;
-        Fr sum = fe_mul(quad_check(fe_sub(w3, x4(w4)), s), r.ap[0]);
-        sum = fe_add(sum, fe_mul(quad_check(fe_sub(w2, x4(w3)), s), r.ap[1]));
-        sum = fe_add(sum, fe_mul(quad_check(fe_sub(w1, x4(w2)), s), r.ap[2]));
-        sum = fe_add(sum, fe_mul(quad_check(fe_sub(w4n, x4(w1)), s), r.ap[3]));
-        total = fe_add(total, fe_mul(sum, QLOAD(QP_QRANGE, i)));
-    }
-    { // logic (k_quotient_turbo_logic)
-        const QuotientSetup& l = *s_logic;
-        const Fr qa = fe_sub(QLOAD(QP_W1, ish), x4(w1));
-        const Fr qb = fe_sub(QLOAD(QP_W2, ish), x4(w2));
-        const Fr qcq = fe_sub(w4n, x4(w4));
-        const Fr sum = fe_add(qa, qb);
-        Fr id = fe_sub(fe_mul(qa, qb), w3);
-        id = fe_mul(fe_add(id, id), s.alpha);
-        id = fe_mul(fe_add(id, quad_check(qa, s)), s.alpha);
-        id = fe_mul(fe_add(id, quad_check(qb, s)), s.alpha);
-        const Fr sum3 = fe_add(fe_add(sum, sum), sum), sum9 = fe_add(fe_add(sum3, sum3), sum3);
-        const Fr sum18 = fe_add(sum9, sum9);
-        Fr sum81 = x4(sum18);
-        sum81 = fe_add(sum81, sum9);
-        const Fr sq = fe_add(fe_sqr(qa), fe_sqr(qb));
-        const Fr sq3 = fe_add(fe_add(sq, sq), sq), sq9 = fe_add(fe_add(sq3, sq3), sq3);
-        const Fr sq18 = fe_add(sq9, sq9);
-        Fr e = fe_add(fe_sub(x4(w3), sum18), s.c81);
-        e = fe_mul(e, w3);
-        e = fe_add(e, fe_add(fe_sub(sq18, sum81), s.c83));
-        e = fe_mul(e, w3);
-        const Fr c3 = fe_add(fe_add(qcq, qcq), qcq), c9 = fe_add(fe_add(c3, c3), c3);
-        Fr tail = fe_sub(fe_add(c3, sum3), fe_add(e, e));
-        tail = fe_add(tail, fe_mul(fe_sub(c9, sum3), qc));
-        id = fe_mul(fe_add(id, tail), l.ap[0]);
-        total = fe_add(total, fe_mul(id, QLOAD(QP_QLOGIC, i)));
+    if constexpr (PARTS == 7) {
+        const Fr w4n = QLOAD(QP_W4, ish);
+        const Fr qc = QLOAD(QP_QC, i);
+        total = arith_part(a, s, i, w1, w2, w3, w4, qc);
+        total = fe_add(total, range_part(a, *s_range, i, w1, w2, w3, w4, w4n));
+        total = fe_add(total, logic_part(a, *s_logic, i, ish, w1, w2, w3, w4, w4n, qc));
+    } else if constexpr (PARTS == 1) {
+        total = arith_part(a, s, i, w1, w2, w3, w4, QLOAD(QP_QC, i));
+    } else if constexpr (PARTS == 2) {
+        total = range_part(a, s, i, w1, w2, w3, w4, QLOAD(QP_W4, ish));
+    } else {
+        total = logic_part(a, s, i, ish, w1, w2, w3, w4, QLOAD(QP_W4, ish), QLOAD(QP_QC, i));
     }
     const Fr q = fe_load<FrP>(a.quotient + i);
     fe_store<FrP>(a.quotient + i, fe_add(q, total));
@@ -836,68 +737,108 @@ int permutation_grand_product(bbg_ctx* ctx, const void* const* d_wires, const vo
     return permutation_grand_product_w(ctx, 4, d_wires, d_sigmas, log2n, challenges, d_z, st);
 }
 
-// which polynomials each widget reads (a null pointer for one of them is an error; the others may be null)
-static const uint32_t WIDGET_NEEDS[WIDGET_COUNT] = {
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_W4) | (1u << QP_Z) | (1u << QP_S1) | (1u << QP_S2) | (1u << QP_S3) |
-        (1u << QP_S4) | (1u << QP_L1),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_W4) | (1u << QP_Q1) | (1u << QP_Q2) | (1u << QP_Q3) | (1u << QP_Q4) |
-        (1u << QP_Q5) | (1u << QP_QM) | (1u << QP_QC) | (1u << QP_QARITH),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_W4) | (1u << QP_Q1) | (1u << QP_Q2) | (1u << QP_Q3) | (1u << QP_Q4) |
-        (1u << QP_Q5) | (1u << QP_QM) | (1u << QP_QC) | (1u << QP_QECC),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_W4) | (1u << QP_QRANGE),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_W4) | (1u << QP_QC) | (1u << QP_QLOGIC),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_Z) | (1u << QP_S1) | (1u << QP_S2) | (1u << QP_S3) | (1u << QP_L1),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_Q1) | (1u << QP_Q2) | (1u << QP_Q3) | (1u << QP_QM) | (1u << QP_QC),
-    (1u << QP_W1) | (1u << QP_W2) | (1u << QP_W3) | (1u << QP_QMIMC_C) | (1u << QP_QMIMC_S),
+// ---------------------------------------------------------------------------------------------- the widgets
+// a pointwise kernel over `threads` threads in blocks of 256
+template <class... P, class... A> static void launch_points(void (*kernel)(P...), size_t threads, hipStream_t st, const A&... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, args...);
+}
+// how a widget is launched on m = 4n points: its kernels one after the other, a thread per point
+template <void (*... K)(QuotientArgs)> static void launch_each(const QuotientArgs& a, size_t m, hipStream_t st)
+{
+    (launch_points(K, m, st, a), ...);
+}
+using ArithRangeLogic = void (*)(QuotientArgs, const QuotientSetup*, const QuotientSetup*);
+template <ArithRangeLogic K> static void launch_part(const QuotientArgs& a, size_t m, hipStream_t st) { launch_points(K, m, st, a, a.s, a.s); }
+template <int WIDTH> static void launch_permutation(const QuotientArgs& a, size_t m, hipStream_t st)
+{
+    launch_points(k_quotient_permutation<WIDTH>, m / PERM_CH, st, a);
+}
+template <int WIDTH> static void launch_permutation29(const QuotientArgs& a, size_t m, hipStream_t st)
+{
+    if (m < ((size_t)1 << 20)) launch_points(q29::k_quotient29_permutation<WIDTH, 1>, m, st, a); // a thread per point (quotient29.hip.h)
+    else launch_points(q29::k_quotient29_permutation<WIDTH, PERM_CH>, m / PERM_CH, st, a);
+}
+
+constexpr uint32_t mask_of(std::initializer_list<int> polys)
+{
+    uint32_t mask = 0;
+    for (int id : polys) mask |= 1u << id;
+    return mask;
+}
+constexpr uint32_t WIRES3 = mask_of({ QP_W1, QP_W2, QP_W3 }), WIRES4 = WIRES3 | mask_of({ QP_W4 });
+// Everything the host knows about a widget, indexed by enum bbg_quotient_widget (include/bbg.h).
+struct Widget {
+    int id;
+    uint32_t reads;    // the polynomials it reads (a null pointer for one of them is an error; the others may be null)
+    uint32_t hand_on;  // its relation count r (alpha_next = alpha_base * alpha^r), or HAND_ON_FOURTH: it ASSIGNS the quotient and must come first
+    void (*launch[2])(const QuotientArgs&, size_t, hipStream_t); // [option quotient_limbs29]
+    bool assigns() const { return hand_on == HAND_ON_FOURTH; }
 };
+static constexpr Widget WIDGETS[WIDGET_COUNT] = {
+    { BBG_WIDGET_PERMUTATION, WIRES4 | mask_of({ QP_Z, QP_S1, QP_S2, QP_S3, QP_S4, QP_L1 }), HAND_ON_FOURTH,
+      { launch_permutation<4>, launch_permutation29<4> } },
+    { BBG_WIDGET_TURBO_ARITHMETIC, WIRES4 | mask_of({ QP_Q1, QP_Q2, QP_Q3, QP_Q4, QP_Q5, QP_QM, QP_QC, QP_QARITH }), 2,
+      { launch_part<k_quotient_turbo_arith_range_logic<1>>, launch_part<q29::k_quotient29_turbo_arith_range_logic<1>> } },
+    { BBG_WIDGET_TURBO_FIXED_BASE, WIRES4 | mask_of({ QP_Q1, QP_Q2, QP_Q3, QP_Q4, QP_Q5, QP_QM, QP_QC, QP_QECC }), 7,
+      { launch_each<k_quotient_turbo_fixed_base_linear, k_quotient_turbo_fixed_base_gate>,
+        launch_each<q29::k_quotient29_turbo_fixed_base_linear, q29::k_quotient29_turbo_fixed_base_gate> } },
+    { BBG_WIDGET_TURBO_RANGE, WIRES4 | mask_of({ QP_QRANGE }), 4,
+      { launch_part<k_quotient_turbo_arith_range_logic<2>>, launch_part<q29::k_quotient29_turbo_arith_range_logic<2>> } },
+    { BBG_WIDGET_TURBO_LOGIC, WIRES4 | mask_of({ QP_QC, QP_QLOGIC }), 4,
+      { launch_part<k_quotient_turbo_arith_range_logic<4>>, launch_part<q29::k_quotient29_turbo_arith_range_logic<4>> } },
+    { BBG_WIDGET_PERMUTATION_3, WIRES3 | mask_of({ QP_Z, QP_S1, QP_S2, QP_S3, QP_L1 }), HAND_ON_FOURTH,
+      { launch_permutation<3>, launch_permutation29<3> } },
+    { BBG_WIDGET_ARITHMETIC, WIRES3 | mask_of({ QP_Q1, QP_Q2, QP_Q3, QP_QM, QP_QC }), 1,
+      { launch_each<k_quotient_standard_arith>, launch_each<q29::k_quotient29_standard_arith> } },
+    { BBG_WIDGET_MIMC, WIRES3 | mask_of({ QP_QMIMC_C, QP_QMIMC_S }), 2, { launch_each<k_quotient_mimc>, launch_each<q29::k_quotient29_mimc> } },
+};
+constexpr bool widgets_in_enum_order()
+{
+    for (int w = 0; w < WIDGET_COUNT; w++)
+        if (WIDGETS[w].id != w) return false;
+    return true;
+}
+static_assert(widgets_in_enum_order(), "WIDGETS is indexed by enum bbg_quotient_widget");
+// the three widgets of a TurboPLONK chain that share one pass over the wires (option quotient_fuse)
+static const ArithRangeLogic FUSED_ARITH_RANGE_LOGIC[2] = { k_quotient_turbo_arith_range_logic<7>, q29::k_quotient29_turbo_arith_range_logic<7> };
+
+// hand_on of a widget list, and (j, e) of every block; false when a value leaves the plan's fields (the serial kernel then, which reads
+// count and hand_on alone)
+static bool widget_plan(const int* widgets, int count, WidgetPlan& plan)
+{
+    memset(&plan, 0, sizeof(plan));
+    plan.count = count;
+    for (int w = 0; w < count; w++) plan.hand_on |= WIDGETS[widgets[w]].hand_on << (4 * w);
+    uint64_t e = 0;
+    int j = 0, bits = 2;
+    for (int w = 0; w < count; w++) {
+        if (j > PLAN_MAX_C4 || e + 7 >= ((uint64_t)1 << PLAN_MAX_BITS)) return false;
+        plan.c4 |= (uint32_t)j << (4 * w);
+        plan.e[w >> 2] |= e << (16 * (w & 3));
+        while ((e + 7) >> bits) bits++;
+        if (j > plan.max_c4) plan.max_c4 = j;
+        if (WIDGETS[widgets[w]].assigns()) {
+            j++;
+            e *= 4;
+        } else {
+            e += WIDGETS[widgets[w]].hand_on;
+        }
+    }
+    plan.table_bits = bits;
+    return true;
+}
 
 static int launch_widget(bbg_ctx* ctx, int widget, const QuotientArgs& a, size_t m, hipStream_t st)
 {
     ProfScope ps(ctx, "quotient_widget", st);
-    if (ctx->quotient_limbs29) { // the 29-bit-limb kernels of quotient29.hip.h
-        switch (widget) {
-        case 0:
-            if (m < ((size_t)1 << 20)) hipLaunchKernelGGL((q29::k_quotient29_permutation<4, 1>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((q29::k_quotient29_permutation<4, PERM_CH>), dim3((unsigned)((m / PERM_CH + 255) / 256)), dim3(256), 0, st, a);
-            break;
-        case 5:
-            if (m < ((size_t)1 << 20)) hipLaunchKernelGGL((q29::k_quotient29_permutation<3, 1>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((q29::k_quotient29_permutation<3, PERM_CH>), dim3((unsigned)((m / PERM_CH + 255) / 256)), dim3(256), 0, st, a);
-            break;
-        case 2:
-            hipLaunchKernelGGL(q29::k_quotient29_turbo_fixed_base_linear, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(q29::k_quotient29_turbo_fixed_base_gate, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-            break;
-        case 1: hipLaunchKernelGGL(q29::k_quotient29_turbo_arith_range_logic<1>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a, a.s, a.s); break;
-        case 3: hipLaunchKernelGGL(q29::k_quotient29_turbo_arith_range_logic<2>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a, a.s, a.s); break;
-        case 4: hipLaunchKernelGGL(q29::k_quotient29_turbo_arith_range_logic<4>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a, a.s, a.s); break;
-        case 6: hipLaunchKernelGGL(q29::k_quotient29_standard_arith, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-        case 7: hipLaunchKernelGGL(q29::k_quotient29_mimc, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-        default: set_error("bbg_quotient_widget_device: unknown widget"); return BBG_E_INVALID;
-        }
-        BBG_HIP(hipGetLastError());
-        return BBG_OK;
-    }
-    switch (widget) {
-    case 0: hipLaunchKernelGGL(k_quotient_permutation<4>, dim3((unsigned)((m / PERM_CH + 255) / 256)), dim3(256), 0, st, a); break;
-    case 5: hipLaunchKernelGGL(k_quotient_permutation<3>, dim3((unsigned)((m / PERM_CH + 255) / 256)), dim3(256), 0, st, a); break;
-    case 6: hipLaunchKernelGGL(k_quotient_standard_arith, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-    case 7: hipLaunchKernelGGL(k_quotient_mimc, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-    case 1: hipLaunchKernelGGL(k_quotient_turbo_arith, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-    case 2:
-        hipLaunchKernelGGL(k_quotient_turbo_fixed_base_linear, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_quotient_turbo_fixed_base_gate, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a);
-        break;
-    case 3: hipLaunchKernelGGL(k_quotient_turbo_range, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(k_quotient_turbo_logic, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a); break;
-    default: set_error("bbg_quotient_widget_device: unknown widget"); return BBG_E_INVALID;
-    }
+    WIDGETS[widget].launch[ctx->quotient_limbs29 ? 1 : 0](a, m, st);
     BBG_HIP(hipGetLastError());
     return BBG_OK;
 }
 
 // `count` widgets in the prover's order (execute_fourth_round, prover.cpp:304-319), each starting from the alpha_base the previous
-// one returned -- chained on the device (set-up block k reads alpha_out of block k-1), no host round trip between them.
+// one returned -- chained on the device (set-up block k starts from the alpha_next of block k-1), no host round trip between them.
 // challenges: 9 Montgomery Fr on the host: alpha_base, alpha, beta, gamma, public_input_delta, g, k1, k2, k3.
 int quotient_widgets_chain(bbg_ctx* ctx, const int* widgets, int count, const void* const* d_polys, unsigned log2_large,
                            const uint64_t* challenges, void* d_quotient, uint64_t* alpha_out, hipStream_t st)
@@ -906,18 +847,15 @@ int quotient_widgets_chain(bbg_ctx* ctx, const int* widgets, int count, const vo
     if (log2_large < 3 || log2_large > 28) { set_error("bbg_quotient_widget_device: need 3 <= log2 of the 4n domain <= 28"); return BBG_E_INVALID; }
     if (!d_polys || !challenges || !d_quotient || !widgets) { set_error("bbg_quotient_widget_device: null argument"); return BBG_E_INVALID; }
     QuotientArgs a;
-    bool extended = false; // d_polys has BBG_QP_EXT_COUNT entries only when a widget that reads the extension is asked for
+    uint32_t read = 0; // d_polys has BBG_QP_EXT_COUNT entries only when a widget that reads the extension is asked for
     for (int w = 0; w < count; w++) {
         if (widgets[w] < 0 || widgets[w] >= WIDGET_COUNT) { set_error("bbg_quotient_widget_device: unknown widget"); return BBG_E_INVALID; }
-        extended = extended || (WIDGET_NEEDS[widgets[w]] >> QP_COUNT) != 0;
+        read |= WIDGETS[widgets[w]].reads;
     }
-    for (int k = 0; k < QP_EXT_COUNT; k++) a.p[k] = (k < QP_COUNT || extended) ? (const Fr*)d_polys[k] : nullptr;
-    for (int w = 0; w < count; w++) {
-        for (int k = 0; k < QP_EXT_COUNT; k++)
-            if (((WIDGET_NEEDS[widgets[w]] >> k) & 1u) && !a.p[k]) {
-                set_error("bbg_quotient_widget_device: a polynomial this widget reads is null");
-                return BBG_E_INVALID;
-            }
+    const bool extended = (read >> QP_COUNT) != 0;
+    for (int k = 0; k < QP_EXT_COUNT; k++) {
+        a.p[k] = (k < QP_COUNT || extended) ? (const Fr*)d_polys[k] : nullptr;
+        if (((read >> k) & 1u) && !a.p[k]) { set_error("bbg_quotient_widget_device: a polynomial this widget reads is null"); return BBG_E_INVALID; }
     }
     QuotientSetup* setups = nullptr;
     int rc = quot_setup_block(ctx, 0, &setups);
@@ -931,27 +869,19 @@ int quotient_widgets_chain(bbg_ctx* ctx, const int* widgets, int count, const vo
     a.mask = (uint32_t)(((size_t)1 << log2_large) - 1);
     a.dc = (const DomainConsts*)dc;
     const size_t m = (size_t)1 << log2_large;
-    // the alpha_base chain runs over the set-up kernels alone (block w reads the alpha_out of block w - 1), so the widget kernels behind
+    // the alpha_base chain runs over the set-up kernels alone (block w starts from the alpha_next of block w - 1), so the widget kernels behind
     // them may run in any order and share passes: arithmetic + range + logic of a TurboPLONK chain go through the data once
+    WidgetPlan plan;
+    if (widget_plan(widgets, count, plan) && ctx->quotient_setup_plan) hipLaunchKernelGGL(k_quotient_setup_plan, dim3(1), dim3(64), 0, st, setups, ch, plan);
+    else hipLaunchKernelGGL(k_quotient_setup_chain, dim3(1), dim3(64), 0, st, setups, ch, plan.count, plan.hand_on);
     int pos_arith = -1, pos_range = -1, pos_logic = -1;
-    {
-        WidgetPlan plan;
-        if (ctx->quotient_setup_plan && widget_plan(widgets, count, plan)) {
-            hipLaunchKernelGGL(k_quotient_setup_plan, dim3(1), dim3(64), 0, st, setups, ch, plan);
-        } else {
-            WidgetChain chain;
-            chain.count = count;
-            for (int w = 0; w < 8; w++) chain.widget[w] = w < count ? widgets[w] : 0;
-            hipLaunchKernelGGL(k_quotient_setup_chain, dim3(1), dim3(64), 0, st, setups, ch, chain);
-        }
-    }
     for (int w = 0; w < count; w++) {
-        if (widgets[w] == 1 && pos_arith < 0) pos_arith = w;
-        if (widgets[w] == 3 && pos_range < 0) pos_range = w;
-        if (widgets[w] == 4 && pos_logic < 0) pos_logic = w;
+        if (widgets[w] == BBG_WIDGET_TURBO_ARITHMETIC && pos_arith < 0) pos_arith = w;
+        if (widgets[w] == BBG_WIDGET_TURBO_RANGE && pos_range < 0) pos_range = w;
+        if (widgets[w] == BBG_WIDGET_TURBO_LOGIC && pos_logic < 0) pos_logic = w;
     }
     // a widget that ASSIGNS the quotient (the permutation widgets) must come first; the prover's chains start with it
-    const bool fuse = ctx->quotient_fuse && pos_arith > 0 && pos_range > 0 && pos_logic > 0 && (widgets[0] == 0 || widgets[0] == 5);
+    const bool fuse = ctx->quotient_fuse && pos_arith > 0 && pos_range > 0 && pos_logic > 0 && WIDGETS[widgets[0]].assigns();
     for (int w = 0; w < count; w++) {
         if (fuse && (w == pos_arith || w == pos_range || w == pos_logic)) continue;
         a.s = setups + w;
@@ -961,14 +891,11 @@ int quotient_widgets_chain(bbg_ctx* ctx, const int* widgets, int count, const vo
     if (fuse) {
         ProfScope ps(ctx, "quotient_widget", st);
         a.s = setups + pos_arith;
-        if (ctx->quotient_limbs29)
-            hipLaunchKernelGGL(q29::k_quotient29_turbo_arith_range_logic<7>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a, setups + pos_range, setups + pos_logic);
-        else
-            hipLaunchKernelGGL(k_quotient_turbo_arith_range_logic, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, a, setups + pos_range, setups + pos_logic);
+        launch_points(FUSED_ARITH_RANGE_LOGIC[ctx->quotient_limbs29 ? 1 : 0], m, st, a, setups + pos_range, setups + pos_logic);
         BBG_HIP(hipGetLastError());
     }
     if (alpha_out) {
-        BBG_HIP(hipMemcpyAsync(alpha_out, &setups[count - 1].alpha_out[widgets[count - 1]], sizeof(Fr), hipMemcpyDeviceToHost, st));
+        BBG_HIP(hipMemcpyAsync(alpha_out, &setups[count - 1].alpha_next, sizeof(Fr), hipMemcpyDeviceToHost, st));
         BBG_HIP(hipStreamSynchronize(st));
     }
     return BBG_OK;

@@ -1,6 +1,6 @@
 // The TurboPLONK / StandardPLONK quotient widgets of quotient.hip on lazily reduced 29-bit limbs (w29.hip.h) -- option "quotient_limbs29"
-// (default 1).  Same identities, same set-up blocks, same [0, 2p) residues in and out as the 32-bit kernels (which stay as the A/B path,
-// option 0); the bounds of every intermediate value are template arguments of its type and checked by the compiler.  Included by
+// (default 1).  Same identities, same set-up blocks, same [0, 2p) residues in and out, same kernel signatures as the 32-bit kernels (which stay
+// as the A/B path, option 0; the widget table of quotient.hip holds the launcher of either family); the bounds of every intermediate value are template arguments of its type and checked by the compiler.  Included by
 // quotient.hip after QuotientArgs / QuotientSetup / QLOAD.
 //
 // Conventions: linear combinations of LOADED values (d = w3 - 4 w4, 9 c - 3 (a + b), ...) stay on the 8 x u32 words (fe_add / fe_sub: exact,

@@ -1,6 +1,6 @@
 """The resident prover's own entry points (csrc/prover.hip) against a model, with no reference-prover binary: the commitment identity of
 every round, rounds 5a (bbg_prover_evaluate), 5b (bbg_prover_linearise) and 6 (bbg_prover_round6) against tests/tools/prover_rounds_model.py,
-and all of it again under every batching option.
+and all of it again under every batching option and every path of round 4's widget chain.
 
 What is held to what.  The handle's polynomials are read back with bbg_prover_read_poly; every commitment must be the MSM of the coefficients
 it claims to commit to (oracle.pippenger at 2^6; from 2^11 bbg_msm, which is pinned to the oracle elsewhere and shares no code with commit()'s
@@ -32,7 +32,8 @@ W_1, Z, SIGMA_1, Q_1, Q_LOGIC = 0, 4, 5, 9, 19
 QUOTIENT, T_1, T_3, T_4, LINEAR, OPENING, SHIFTED_OPENING, Q_MIMC_COEFFICIENT, Q_MIMC_SELECTOR = 21, 22, 24, 25, 26, 27, 28, 29, 30
 FLAVOUR_MIMC = 2
 SENTINEL = 0x5A5A5A5A5A5A5A5A
-DEFAULTS = {"prover_msm_batch": 4, "prover_tail_window": 0, "msm_window": 0, "poly_limbs29": 1, "prover_ntt_batch": 1, "prover_early_cosets": -1}
+DEFAULTS = {"prover_msm_batch": 4, "prover_tail_window": 0, "msm_window": 0, "poly_limbs29": 1, "prover_ntt_batch": 1, "prover_early_cosets": -1,
+            "quotient_limbs29": 1, "quotient_fuse": 1, "quotient_setup_plan": 1}
 SHAPES = {"6w3": (6, 3, False), "6w4": (6, 4, False), "11w4": (11, 4, False), "12w3": (12, 3, False), "12mimc": (12, 3, True)}
 ROUND6_DEFAULT = (14, 5)  # the term counts of a TurboPLONK proof (bench.py prover_shaped)
 
@@ -438,6 +439,17 @@ def test_tail_window_does_not_override_msm_window(shapes, bbg):
 def test_option_poly_limbs29(shapes, bbg, name, limbs29):
     """0 = the evaluations, r(X) and both opening sums on the 32-bit kernels (k_multi_eval_partial, k_poly_lincomb, k_eval_partial)."""
     option_row(shapes(name), bbg, f"{name} poly_limbs29={limbs29}", poly_limbs29=limbs29)
+
+
+@pytest.mark.parametrize("limbs29,fuse,plan", [(1, 0, 1), (0, 1, 1), (0, 0, 1), (1, 1, 0), (0, 0, 0)])
+@pytest.mark.parametrize("name", ["6w4", "6w3", "11w4", "12mimc"])
+def test_option_quotient_paths(shapes, bbg, name, limbs29, fuse, plan):
+    """Round 4's widget chain (csrc/quotient.hip) by every path: 29-bit or 32-bit limbs, arithmetic + range + logic fused or a kernel each, the
+    set-up blocks by a wave's lanes or by one lane's chain -- blocks 1 to 4 of a chain start from what the block before handed on, which the
+    one-widget tests never reach.  6w4: 4n = 256, one block exactly, the shifted rows wrap inside it; 6w3: the chain 5, 6, nothing to fuse;
+    11w4: 32 blocks, the wrap from the last to the first; 12mimc: the chain 5, 7, 6."""
+    what = f"{name} quotient_limbs29={limbs29} quotient_fuse={fuse} quotient_setup_plan={plan}"
+    option_row(shapes(name), bbg, what, quotient_limbs29=limbs29, quotient_fuse=fuse, quotient_setup_plan=plan)
 
 
 def test_option_unbatched_transforms_and_early_cosets(shapes, bbg):
