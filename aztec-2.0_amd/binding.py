@@ -101,6 +101,8 @@ def load_library():
         "bbg_cells_values": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
         "bbg_cells_recover_device": (cint, [vp, vp, sz, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
         "bbg_cells_recover": (cint, [vp, vp, sz, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
+        "bbg_cells_verify_reduce_device": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp]),
+        "bbg_cells_verify_reduce": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "bbg_ntt": (cint, [vp, vp, ctypes.c_uint, cint, sz, vp]),
         "bbg_coset_fft_extend": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp]),
         "bbg_quotient_widget_device": (cint, [vp, cint, vp, ctypes.c_uint, vp, vp, vp]),
@@ -190,6 +192,7 @@ EXPORTED_SYMBOLS = [
     "bbg_g1_ntt", "bbg_g1_ntt_device", "bbg_open_all_prepare", "bbg_open_all_device", "bbg_open_all", "bbg_open_all_device_bytes", "bbg_open_all_free",
     "bbg_open_all_prepare_cells", "bbg_open_all_count",
     "bbg_cells_values_device", "bbg_cells_values", "bbg_cells_recover_device", "bbg_cells_recover",
+    "bbg_cells_verify_reduce_device", "bbg_cells_verify_reduce",
 ]
 
 
@@ -514,6 +517,36 @@ class Bbg:
         ids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
         self._ck(self.lib.bbg_cells_recover_device(self.ctx, ids.ctypes.data, ids.shape[0], ctypes.c_void_p(d_values), log2n, log2cell, count,
                                                    ctypes.c_void_p(d_out_coeffs)))
+
+    # ---- a batch of cell proofs reduced to the two points of one pairing check (csrc/cells_verify.hip)
+    def cells_verify_reduce(self, srs, log2n, log2cell, commitments, commitment_ids, cell_ids, values, proofs, rho):
+        """K cells: cell k has commitment commitments[commitment_ids[k]], cell index cell_ids[k], the l values values[k l : (k + 1) l] and the
+        proof proofs[k].  Returns (2, 8) canonical affine words (L, R): every proof is valid iff e(L, [x^l]_2) = e(R, [1]_2), up to the choice
+        of rho (4 Montgomery words).  A point off the curve raises BbgError (bbg_cells_verify_reduce)."""
+        com, prf, v = _u64(commitments, 8), _u64(proofs, 8), _u64(values, 4)
+        cids = np.ascontiguousarray(commitment_ids, dtype=np.uint32).reshape(-1)
+        mids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        K = mids.shape[0]
+        if cids.shape[0] != K or prf.shape[0] != K or v.shape[0] != K << log2cell:
+            raise ValueError(f"expected {K} commitment ids and proofs and {K << log2cell} values")
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        out = np.zeros((2, 8), dtype=np.uint64)
+        self._ck(self.lib.bbg_cells_verify_reduce(self.ctx, srs.handle, log2n, log2cell, com.ctypes.data, com.shape[0], cids.ctypes.data, mids.ctypes.data, K,
+                                                  v.ctypes.data, prf.ctypes.data, rho.ctypes.data, out.ctypes.data))
+        return out
+
+    def cells_verify_reduce_device(self, srs, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, d_values, d_proofs, rho, d_out,
+                                   d_off_curve=None):
+        """Device pointers (ncom x 64 B, K x l x 32 B, K x 64 B in; 128 B and, optionally, one uint32 out), the ids and rho on the host;
+        asynchronous on the context stream (bbg_cells_verify_reduce_device)."""
+        cids = np.ascontiguousarray(commitment_ids, dtype=np.uint32).reshape(-1)
+        mids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        if cids.shape[0] != mids.shape[0]:
+            raise ValueError("one commitment id and one cell id per cell")
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        self._ck(self.lib.bbg_cells_verify_reduce_device(self.ctx, srs.handle, log2n, log2cell, ctypes.c_void_p(d_commitments), ncom, cids.ctypes.data,
+                                                         mids.ctypes.data, mids.shape[0], ctypes.c_void_p(d_values), ctypes.c_void_p(d_proofs),
+                                                         rho.ctypes.data, ctypes.c_void_p(d_out), ctypes.c_void_p(d_off_curve) if d_off_curve else None))
 
     # ---- NTT
     def ntt(self, coeffs, op=FFT, generator_size=0, constant=None):

@@ -998,6 +998,49 @@ int bbg_cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const ui
     return BBG_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ cell proofs to one pairing check (cells_verify.hip)
+int bbg_cells_verify_reduce_device(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                                   const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs,
+                                   const uint64_t rho[4], void* d_out, void* d_off_curve)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return cells_verify_reduce(ctx, srs, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, d_out, d_off_curve,
+                               ctx->stream);
+}
+
+int bbg_cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const uint64_t* commitments, size_t ncom,
+                            const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const uint64_t* values, const uint64_t* proofs,
+                            const uint64_t rho[4], uint64_t out[16])
+{
+    CHECK_CTX(ctx);
+    if (!commitments || !values || !proofs || !out) { set_error("bbg_cells_verify_reduce: null argument"); return BBG_E_INVALID; }
+    int rc = cells_verify_check("bbg_cells_verify_reduce", ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t com_bytes = ncom * 64, proof_bytes = K * 64, value_bytes = K * ((size_t)32 << log2cell);
+    rc = ctx->staging.ensure(com_bytes + proof_bytes + value_bytes + 256);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p; // commitments | proofs | values | L, R | the off-curve count
+    char *d_proofs = st + com_bytes, *d_values = d_proofs + proof_bytes, *d_res = d_values + value_bytes;
+    BBG_HIP(hipMemcpyAsync(st, commitments, com_bytes, hipMemcpyHostToDevice, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(d_proofs, proofs, proof_bytes, hipMemcpyHostToDevice, ctx->stream));
+    BBG_HIP(hipMemcpyAsync(d_values, values, value_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = cells_verify_reduce(ctx, srs, log2n, log2cell, st, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, d_res, d_res + 128, ctx->stream);
+    if (rc) return rc;
+    uint64_t res[18]; // L, R, then the count in the low word of res[16]
+    BBG_HIP(hipMemcpyAsync(res, d_res, 128 + 4, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    uint32_t off_curve = 0;
+    memcpy(&off_curve, res + 16, 4);
+    if (off_curve) {
+        set_error("bbg_cells_verify_reduce: " + std::to_string(off_curve) + " of the commitments and proofs are not on the curve");
+        return BBG_E_INVALID;
+    }
+    memcpy(out, res, 128);
+    return BBG_OK;
+}
+
 int bbg_srs_retain(bbg_srs* srs)
 {
     if (!srs) { set_error("bbg_srs_retain: null handle"); return BBG_E_INVALID; }

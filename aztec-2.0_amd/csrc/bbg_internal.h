@@ -197,7 +197,8 @@ struct bbg_ctx {
     int batch_mul_glv = 1;           // option "batch_mul_glv": 1 = windowed GLV (xyzz_mul_glv), 0 = the bit-serial double-and-add (xyzz_mul_fr), A/B
     long batch_mul_lanes = 1L << 17; // option "batch_mul_lanes": lanes of the variable-base kernels = tables held (a multiple of 64; 2^17 = two waves per SIMD)
     // cells.hip: the tables of one bbg_cells_recover call (roots, points, Z, slot map) or the working array of bbg_cells_values, and the pinned
-    // host array the slot map and id lists of a call are built in (cells_copied: the copy of the last call has read it)
+    // host array the slot map and id lists of a call are built in (cells_copied: the copy of the last call has read it); cells_verify.hip: the
+    // working set of one bbg_cells_verify_reduce call, its group lists staged through the same pinned array
     bbg::DevBuf cells_work;
     void* cells_pinned = nullptr;
     size_t cells_pinned_bytes = 0;
@@ -369,4 +370,14 @@ int cells_values(bbg_ctx* ctx, const void* d_coeffs, unsigned log2n, unsigned lo
 // values lie at d_values + ((p K + k) l) x 32 B; canonical.  d_out_coeffs is also the working array of the three transforms.  Queues only.
 int cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* d_values, unsigned log2n, unsigned log2cell, size_t count,
                   void* d_out_coeffs, hipStream_t stream);
+// ctx->cells_pinned with at least `bytes`, once the copy of the call before has read it; the caller records ctx->cells_copied behind its copy
+int cells_pinned_ensure(bbg_ctx* ctx, size_t bytes);
+// cells_verify.hip.  The argument checks that need no device pointer: BBG_E_INVALID with the error text set.
+int cells_verify_check(const char* who, const bbg_ctx* ctx, const bbg_srs* srs, unsigned log2n, unsigned log2cell, size_t ncom, const uint32_t* commitment_ids,
+                       const uint32_t* cell_ids, size_t K, const uint64_t* rho);
+// d_out[0] = L = sum_k rho^k pi_k, d_out[1] = R (canonical affine, aff_inf() for infinity); *d_off_curve (may be null) = the finite
+// commitments and proofs that are not on the curve.  The id arrays are HOST arrays, read before the call returns.  Queues only.
+int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom, const uint32_t* commitment_ids,
+                        const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho, void* d_out, void* d_off_curve,
+                        hipStream_t stream);
 } // namespace bbg

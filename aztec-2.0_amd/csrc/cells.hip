@@ -163,6 +163,27 @@ int cells_check_ids(const char* who, const uint32_t* cell_ids, size_t K, unsigne
     return BBG_OK;
 }
 
+// The context's pinned array with at least `bytes`, free to be written: the event says when the copy of the call before this one is
+// through with it.  The caller records ctx->cells_copied behind its own copy.
+int cells_pinned_ensure(bbg_ctx* ctx, size_t bytes)
+{
+    if (ctx->cells_pinned_bytes < bytes) {
+        if (ctx->cells_pinned) {
+            BBG_HIP(hipEventSynchronize(ctx->cells_copied));
+            void* old = ctx->cells_pinned;
+            ctx->cells_pinned = nullptr;
+            ctx->cells_pinned_bytes = 0;
+            BBG_HIP(hipHostFree(old));
+        }
+        if (!ctx->cells_copied) BBG_HIP(hipEventCreateWithFlags(&ctx->cells_copied, hipEventDisableTiming));
+        BBG_HIP(hipHostMalloc(&ctx->cells_pinned, bytes, hipHostMallocDefault));
+        ctx->cells_pinned_bytes = bytes;
+    } else {
+        BBG_HIP(hipEventSynchronize(ctx->cells_copied));
+    }
+    return BBG_OK;
+}
+
 int cells_values(bbg_ctx* ctx, const void* d_coeffs, unsigned log2n, unsigned log2cell, size_t count, void* d_out, hipStream_t st)
 {
     if (!d_coeffs || !d_out) { set_error("bbg_cells_values_device: null argument"); return BBG_E_INVALID; }
@@ -201,22 +222,8 @@ int cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* 
     Fr* z = pts + 2 * r;
     int32_t* slot = (int32_t*)(z + 2 * r);
     uint32_t* lists = (uint32_t*)(slot + r);
-    // slot map and id lists, built in the context's pinned array (the copy below may run after this call has returned); the event says when
-    // the copy of the call before this one is through with it
-    if (ctx->cells_pinned_bytes < r * 8) {
-        if (ctx->cells_pinned) {
-            BBG_HIP(hipEventSynchronize(ctx->cells_copied));
-            void* old = ctx->cells_pinned;
-            ctx->cells_pinned = nullptr;
-            ctx->cells_pinned_bytes = 0;
-            BBG_HIP(hipHostFree(old));
-        }
-        if (!ctx->cells_copied) BBG_HIP(hipEventCreateWithFlags(&ctx->cells_copied, hipEventDisableTiming));
-        BBG_HIP(hipHostMalloc(&ctx->cells_pinned, r * 8, hipHostMallocDefault));
-        ctx->cells_pinned_bytes = r * 8;
-    } else {
-        BBG_HIP(hipEventSynchronize(ctx->cells_copied));
-    }
+    // slot map and id lists, built in the context's pinned array (the copy below may run after this call has returned)
+    if (int rc = cells_pinned_ensure(ctx, r * 8)) return rc;
     int32_t* h_slot = (int32_t*)ctx->cells_pinned;
     uint32_t* h_lists = (uint32_t*)(h_slot + r);
     for (size_t m = 0; m < r; m++) h_slot[m] = -1;

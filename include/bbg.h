@@ -215,8 +215,10 @@ int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_
  * and r instead of 2n and n.  Its memory: 2n x 64 B of transformed points, 2n x 128 B of products, 2n x 32 B of scalars, 2r x 128 B +
  * r x 128 B of working arrays (bbg_open_all_device_bytes), outside bbg_memory_report like the all-points handle's.
  *   The VALUES of cell m are f(w_n^(m + r t)), t < l: bbg_ntt(BBG_FFT) of the n coefficients, read at index m with stride r.
- * bbg_cells_values writes them cell by cell, and bbg_cells_recover gives the coefficients back from any K of the r cells (below).  This
- * library does not verify: checking a cell proof pairs against [x^l]_2, a G2 point that this library does not make. */
+ * bbg_cells_values writes them cell by cell, and bbg_cells_recover gives the coefficients back from any K of the r cells (below).
+ * Verification: bbg_cells_verify_reduce (below) reduces any batch of cell proofs to two G1 points L, R with e(L, [x^l]_2) = e(R, [1]_2)
+ * iff every proof is valid.  The caller still owes that one two-pair pairing against [x^l]_2, a G2 point this library does not make, and
+ * the choice of the challenge rho. */
 int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
 /* The number of proofs a call writes: n >> log2cell (n for a handle of bbg_open_all_prepare). */
 int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs);
@@ -255,6 +257,40 @@ int bbg_cells_recover_device(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, c
 /* Host-buffer form: upload, compute, download; synchronous. */
 int bbg_cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const uint64_t* values, unsigned log2n, unsigned log2cell, size_t count,
                       uint64_t* out_coeffs);
+/* ---- a batch of cell proofs reduced to ONE pairing check (csrc/cells_verify.hip): everything a verifier of cell proofs computes in G1 and
+ *      Fr, up to the pairing, which stays the caller's.  A batch has ncom commitments C_c and K cells; cell k < K carries a commitment index
+ *      commitment_ids[k] < ncom, a cell index cell_ids[k] < r, the l values of that cell at values[k l .. k l + l) in bbg_cells_values'
+ *      order within the cell, and a proof pi_k (what bbg_open_all_device writes for that cell).  With I_k the interpolant of degree < l
+ *      through the values, s_b the first l points of `srs` and rho the caller's challenge, the call writes
+ *          L = sum_k rho^k pi_k
+ *          R = sum_k rho^k ( C_(c_k) - sum_(b<l) I_k,b s_b + phi^(m_k) pi_k )
+ *      and over a powers string every proof is valid iff (with overwhelming probability over rho) e(L, [x^l]_2) = e(R, [1]_2): one
+ *      two-pair pairing whatever K is.  rho must be unpredictable to whoever made the proofs (Fiat-Shamir over the whole batch is the
+ *      caller's business); rho^0 = 1 also for rho = 0.  log2cell = 0 is batched verification of single-point openings (bbg_open_all's
+ *      proofs, the values those of bbg_ntt).  The coefficients of sum_k rho^k I_k cost ONE inverse transform at n, not one per cell: they
+ *      are r times the first l coefficients of iNTT_n of the rho-weighted values laid out in domain order.
+ *        Conventions: Fr inputs (values, rho) Montgomery, any representative in [0, 2r_mod); points 64-byte Montgomery affine, any
+ *      representative in [0, 2p) per coordinate, the affine encoding of infinity accepted as data (every proof of a polynomial of degree
+ *      < l, the commitment of the zero polynomial).  out: L then R, canonical affine; an output at infinity is written exactly as bbg_g1_ntt
+ *      writes it.  Duplicate (commitment, cell) pairs are legal, and so are commitments no cell refers to.  The reduction is a function of
+ *      its inputs, valid or not.
+ *        Curve check: every finite commitment and proof is tested against y^2 = x^3 + 3 as it is loaded (a verifier that accepts points off
+ *      the curve is unsound).  The device form writes the number that fail to *d_off_curve (uint32) when that is not NULL; L and R are
+ *      then unspecified, but nothing else is affected.  The host form returns BBG_E_INVALID for a non-zero count and leaves `out` untouched.
+ *        BBG_E_INVALID with nothing queued and the outputs untouched: a null pointer (d_off_curve excepted), K = 0, ncom = 0, K or ncom
+ *      above 2^30, an id out of range, log2n outside 1 .. 28, log2cell > log2n - 1, l above the SRS length, an SRS on another device, an
+ *      output that overlaps an input or the other output.  The id arrays are HOST arrays, read before the call returns.  The device form
+ *      queues on the context stream and does not synchronise the host once the working memory has its size: 32 n + 256 r + 160 (K + ncom)
+ *      bytes and the group lists in the cells buffer, the lanes' tables of bbg_g1_batch_mul (both `scratch` in bbg_memory_report, released
+ *      by bbg_memory_trim), the domain's tables and the MSM's arena.  Timed under "cells_verify_powers", "cells_verify_fold",
+ *      "cells_verify_mul", "cells_verify_segsum", "cells_verify_phi", "cells_verify_finish", beside "ntt_pass" and the MSM's names. ---- */
+int bbg_cells_verify_reduce_device(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                                   const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs,
+                                   const uint64_t rho[4], void* d_out, void* d_off_curve);
+/* Host-buffer form: upload, compute, download; synchronous. */
+int bbg_cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const uint64_t* commitments, size_t ncom,
+                            const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const uint64_t* values, const uint64_t* proofs,
+                            const uint64_t rho[4], uint64_t out[16]);
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes);
 /* Releases the handle and its device memory (a device synchronisation); must precede bbg_destroy of its context. */
 void bbg_open_all_free(struct bbg_open_all* h);
@@ -519,7 +555,8 @@ typedef struct bbg_memory_info {
     size_t ntt_tables;     /* per-domain twiddle / coset tables (5 x 32n bytes per prepared size) */
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
     size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
-                              variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover */
+                              variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover,
+                              the working set of bbg_cells_verify_reduce */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
@@ -572,7 +609,8 @@ int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
 /* Per-kernel timing with HIP events recorded on the launch stream.  Names: "msm_recode", "msm_sort", "msm_offsets",
  * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul",
  * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum",
- * "cells_gather", "cells_z", "cells_scatter", "cells_divide", "cells_canon".  enable(…, 1) clears previous samples. */
+ * "cells_gather", "cells_z", "cells_scatter", "cells_divide", "cells_canon", "cells_verify_powers", "cells_verify_fold", "cells_verify_mul",
+ * "cells_verify_segsum", "cells_verify_phi", "cells_verify_finish".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
