@@ -96,6 +96,9 @@ def load_library():
         "bbg_open_all_device": (cint, [vp, vp, vp]),
         "bbg_open_all": (cint, [vp, vp, vp]),
         "bbg_open_all_device_bytes": (cint, [vp, ctypes.POINTER(sz)]),
+        "bbg_open_all_batch_reserve": (cint, [vp, sz]),
+        "bbg_open_all_batch_device": (cint, [vp, vp, sz, vp]),
+        "bbg_open_all_batch": (cint, [vp, vp, sz, vp]),
         "bbg_open_all_free": (None, [vp]),
         "bbg_cells_values_device": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
         "bbg_cells_values": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
@@ -191,6 +194,7 @@ EXPORTED_SYMBOLS = [
     "bbg_prover_evaluate_lagrange",
     "bbg_g1_ntt", "bbg_g1_ntt_device", "bbg_open_all_prepare", "bbg_open_all_device", "bbg_open_all", "bbg_open_all_device_bytes", "bbg_open_all_free",
     "bbg_open_all_prepare_cells", "bbg_open_all_count",
+    "bbg_open_all_batch_reserve", "bbg_open_all_batch_device", "bbg_open_all_batch",
     "bbg_cells_values_device", "bbg_cells_values", "bbg_cells_recover_device", "bbg_cells_recover",
     "bbg_cells_verify_reduce_device", "bbg_cells_verify_reduce",
 ]
@@ -278,7 +282,27 @@ class OpenAll:
         """Device pointers, d_out of count x 64 B; asynchronous on the context stream (bbg_open_all_device)."""
         self._owner._ck(self._owner.lib.bbg_open_all_device(self.handle, ctypes.c_void_p(d_coeffs), ctypes.c_void_p(d_out)))
 
+    def reserve_batch(self, polys):
+        """The batch workspace for `polys` polynomials at a time, at most the library's cap; 0 releases it (bbg_open_all_batch_reserve)."""
+        self._owner._ck(self._owner.lib.bbg_open_all_batch_reserve(self.handle, polys))
+
+    def open_batch(self, coeffs):
+        """(polys, count, 8) canonical affine proofs for (polys, n, 4) Montgomery coefficients (bbg_open_all_batch): out[p] is what open
+        returns for coeffs[p]."""
+        c = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        if c.ndim != 3 or c.shape[0] < 1 or c.shape[1:] != (1 << self.log2n, 4):
+            raise ValueError(f"expected (polys, {1 << self.log2n}, 4) uint64 limbs, got {c.shape}")
+        out = np.zeros((c.shape[0], self.count, 8), dtype=np.uint64)
+        self._owner._ck(self._owner.lib.bbg_open_all_batch(self.handle, c.ctypes.data, c.shape[0], out.ctypes.data))
+        return out
+
+    def open_batch_device(self, d_coeffs, count, d_out):
+        """Device pointers: count x n x 32 B in, count x proofs x 64 B out, polynomial-major; asynchronous on the context stream
+        (bbg_open_all_batch_device)."""
+        self._owner._ck(self._owner.lib.bbg_open_all_batch_device(self.handle, ctypes.c_void_p(d_coeffs), count, ctypes.c_void_p(d_out)))
+
     def device_bytes(self):
+        """The handle's device memory, the batch workspace included while it is reserved (bbg_open_all_device_bytes)."""
         b = ctypes.c_size_t()
         self._owner._ck(self._owner.lib.bbg_open_all_device_bytes(self.handle, ctypes.byref(b)))
         return int(b.value)

@@ -931,7 +931,44 @@ int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_a
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes)
 {
     if (!h || !bytes) { set_error("bbg_open_all_device_bytes: null argument"); return BBG_E_INVALID; }
-    *bytes = open_all_bytes(h->log2n, h->log2cell);
+    *bytes = open_all_bytes(h->log2n, h->log2cell) + h->batch_cap * open_all_batch_poly_bytes(h->log2n, h->log2cell);
+    return BBG_OK;
+}
+
+int bbg_open_all_batch_reserve(struct bbg_open_all* h, size_t polys)
+{
+    if (!h) { set_error("bbg_open_all_batch_reserve: null argument"); return BBG_E_INVALID; }
+    CHECK_CTX(h->ctx);
+    std::lock_guard<std::mutex> lk(h->ctx->mu);
+    return open_all_batch_reserve(h, polys);
+}
+
+int bbg_open_all_batch_device(struct bbg_open_all* h, const void* d_coeffs, size_t count, void* d_out_affine)
+{
+    if (!h || !d_coeffs || !d_out_affine) { set_error("bbg_open_all_batch_device: null argument"); return BBG_E_INVALID; }
+    if (count == 0) { set_error("bbg_open_all_batch_device: count must be at least 1"); return BBG_E_INVALID; }
+    CHECK_CTX(h->ctx);
+    std::lock_guard<std::mutex> lk(h->ctx->mu);
+    return open_all_batch_run(h, d_coeffs, count, d_out_affine, h->ctx->stream);
+}
+
+int bbg_open_all_batch(struct bbg_open_all* h, const uint64_t* coeffs, size_t count, uint64_t* out_affine)
+{
+    if (!h || !coeffs || !out_affine) { set_error("bbg_open_all_batch: null argument"); return BBG_E_INVALID; }
+    if (count == 0) { set_error("bbg_open_all_batch: count must be at least 1"); return BBG_E_INVALID; }
+    bbg_ctx* ctx = h->ctx;
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t n = (size_t)1 << h->log2n, proofs = n >> h->log2cell;
+    if (count > ((size_t)1 << 40) / n) { set_error("bbg_open_all_batch: count x 2^log2n is out of range"); return BBG_E_INVALID; }
+    int rc = ctx->staging.ensure(count * n * 96);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p; // proofs | coefficients
+    BBG_HIP(hipMemcpyAsync(st + count * n * 64, coeffs, count * n * 32, hipMemcpyHostToDevice, ctx->stream));
+    rc = open_all_batch_run(h, st + count * n * 64, count, st, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out_affine, st, count * proofs * 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
     return BBG_OK;
 }
 

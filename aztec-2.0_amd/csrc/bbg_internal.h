@@ -223,6 +223,11 @@ struct bbg_open_all {
     void* work1 = nullptr;  // n x 128 B XYZZ: the forward transform's; cells: r x 128 B
     void* c_hat = nullptr;  // 2n x 32 B Fr
     void* sum = nullptr;    // cells only: 2r x 128 B XYZZ, the summed products = the inverse transform's working array
+    // the batched calls' workspace (bbg_open_all_batch_reserve): batch_cap copies of work2 | work1 | sum | c_hat in ONE allocation, every
+    // array polynomial-major.  Owned by the handle like the buffers above, none of which a batched call touches.
+    void* batch_ws = nullptr;
+    size_t batch_cap = 0;
+    bool batch_lds_attr = false; // the LDS transform's dynamic-LDS limit is raised on this handle's device (hipFuncSetAttribute is per device)
 };
 
 struct bbg_srs {
@@ -342,6 +347,9 @@ int ecntt_load(const void* d_src, unsigned log2n, void* d_work, hipStream_t stre
 int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t stream);
 // the forward stages of the 2^(log2n - log2block) contiguous blocks of 2^log2block points of d_work, each block a transform of its own
 int ecntt_stages_blocks(bbg_ctx* ctx, void* d_work, unsigned log2n, unsigned log2block, hipStream_t stream);
+// `count` >= 1 independent transforms of 2^log2block points on the contiguous blocks of d_work (each bit-reversed within itself), all
+// stages, either direction, one launch per stage
+int ecntt_stages_batch(bbg_ctx* ctx, void* d_work, unsigned log2block, size_t count, int inverse, hipStream_t stream);
 int ecntt_normalize(bbg_ctx* ctx, const void* d_work, size_t n, void* d_out, unsigned* d_inf_flag, hipStream_t stream);
 // fixed_base.hip: d_out[i] = d_scalars[i] * B (64 B canonical affine, aff_inf() for an infinite result) from the context's table of B's
 // multiples, which is built on first use and rebuilt for another base.  base_affine: HOST, NULL = the generator; BBG_E_INVALID when it is
@@ -360,6 +368,13 @@ int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, str
 int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
 int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t stream);
 size_t open_all_bytes(unsigned log2n, unsigned log2cell);
+// the batched calls: the workspace of one polynomial, the polynomials one workspace may hold (OPEN_BATCH_BUDGET), the
+// reservation (0 releases; waits for the device when it replaces one) and the call itself, which walks `count` polynomials in chunks of
+// the reservation and queues only
+size_t open_all_batch_poly_bytes(unsigned log2n, unsigned log2cell);
+size_t open_all_batch_cap(unsigned log2n, unsigned log2cell);
+int open_all_batch_reserve(struct bbg_open_all* h, size_t polys);
+int open_all_batch_run(struct bbg_open_all* h, const void* d_coeffs, size_t count, void* d_out, hipStream_t stream);
 void open_all_release(struct bbg_open_all* h);
 // cells.hip.  The checks return BBG_E_INVALID with the error text set; `who` names the entry point in it.
 int cells_check_shape(const char* who, unsigned log2n, unsigned log2cell, size_t count);

@@ -29,7 +29,9 @@
 //     transform out[k] = sum_j w_n^(jk) P_j: twiddles from the table of root^(2^b), and no n^-1 in the last stage;
 //   * k_ecntt_normalize<true> stores a point at infinity as aff_inf() and raises no flag;
 //   * ecntt_stages_blocks stops the forward stages early: many independent transforms of contiguous blocks in one pass (the cell handle
-//     of open_all.hip prepares its strings that way).
+//     of open_all.hip prepares its strings that way);
+//   * ecntt_stages_batch runs ALL stages of a small domain over any number of contiguous blocks, in either direction: the stage kernels
+//     take the number of butterflies, not the array length (the batched calls of open_all.hip).
 #include "bbg_internal.h"
 #include "curve.hip.h"
 #include "ecntt.hip.h" // bit_reverse
@@ -54,12 +56,15 @@ __global__ void __launch_bounds__(256) k_ecntt_load(const Affine* __restrict__ s
 #define BBG_ECNTT_OCC 2
 #endif
 // INV: the inverse transform (twiddles w_n^-1, n^-1 folded into the last stage); the forward one ignores `last`.
+// `butterflies` is n / 2 for one transform; count n / 2 walks `count` contiguous blocks of n points, each a transform of its own: i runs
+// on through block after block and the twiddle depends on j alone (ecntt_stages_batch).  Registers: profiles/open_batch.txt.
 template <bool INV>
-__global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last)
+__global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last,
+                                                                   size_t butterflies)
 {
     if (!INV) last = 0;
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ((size_t)1 << (log2n - 1))) return;
+    if (t >= butterflies) return;
     const size_t m = (size_t)1 << s;
     const size_t j = t & (m - 1);
     const size_t i = ((t >> s) << (s + 1)) + j;
@@ -80,7 +85,7 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage(Xyzz* __restr
 // normalisation (the same group elements in another XYZZ representation).
 template <bool INV>
 __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __restrict__ work, const DomainConsts* __restrict__ dc, unsigned log2n, unsigned s, int last,
-                                                                       Xyzz* __restrict__ tables)
+                                                                       size_t butterflies, Xyzz* __restrict__ tables)
 {
     if (!INV) last = 0;
     const size_t lanes = (size_t)gridDim.x * blockDim.x;
@@ -88,7 +93,7 @@ __global__ void __launch_bounds__(64, BBG_ECNTT_OCC) k_ecntt_stage_glv(Xyzz* __r
     Xyzz* table = tables + (size_t)blockIdx.x * 64 * GLV_TABLE; // the wave's 64 tables (blocks of one wave): wave-uniform
     const size_t m = (size_t)1 << s;
 #pragma unroll 1
-    for (size_t t = lane; t < ((size_t)1 << (log2n - 1)); t += lanes) {
+    for (size_t t = lane; t < butterflies; t += lanes) {
         const size_t j = t & (m - 1);
         const size_t i = ((t >> s) << (s + 1)) + j;
         Xyzz b = xyzz_load(work + i + m);
@@ -141,19 +146,19 @@ int ecntt_load(const void* d_src, unsigned log2n, void* d_work, hipStream_t st)
     return BBG_OK;
 }
 
-// The first `stages` of the log2n stages on `st`, in place on d_work.  The lanes' tables come from the context (var_base_tables) under
-// "ecntt_mul" = 1.
-static int ecntt_stages_upto(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, unsigned stages, hipStream_t st)
+// The first `stages` of the log2n stages on `st`, in place on d_work, over `count` contiguous blocks of n = 2^log2n points: count n / 2
+// butterflies per stage.  The lanes' tables come from the context (var_base_tables) under "ecntt_mul" = 1.
+static int ecntt_stages_upto(bbg_ctx* ctx, void* d_work, unsigned log2n, size_t count, int inverse, unsigned stages, hipStream_t st)
 {
     if (log2n < 1 || log2n > 28) { set_error("ecntt: log2n out of range (1 .. 28)"); return BBG_E_INVALID; }
+    const size_t butterflies = count << (log2n - 1);
     void* consts = nullptr;
     int rc = ntt_domain_consts(ctx, log2n, &consts); // root^(2^b), root_inv^(2^b) and n^-1 of the scalar NTT's domain
     if (rc) return rc;
-    const size_t n = (size_t)1 << log2n;
     size_t lanes = 0;
     void* tables = nullptr;
     if (ctx->ecntt_mul) { // the lanes' tables of odd multiples (var_base.hip)
-        rc = var_base_tables(ctx, n / 2, &lanes, &tables);
+        rc = var_base_tables(ctx, butterflies, &lanes, &tables);
         if (rc) return rc;
     }
     auto glv = inverse ? k_ecntt_stage_glv<true> : k_ecntt_stage_glv<false>;
@@ -161,9 +166,10 @@ static int ecntt_stages_upto(bbg_ctx* ctx, void* d_work, unsigned log2n, int inv
     for (unsigned s = 0; s < stages; s++) {
         const int last = s + 1 == log2n ? 1 : 0;
         if (ctx->ecntt_mul)
-            hipLaunchKernelGGL(glv, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last, (Xyzz*)tables);
+            hipLaunchKernelGGL(glv, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last, butterflies,
+                               (Xyzz*)tables);
         else
-            hipLaunchKernelGGL(serial, dim3(grid_for(n / 2, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last);
+            hipLaunchKernelGGL(serial, dim3(grid_for(butterflies, 64)), dim3(64), 0, st, (Xyzz*)d_work, (const DomainConsts*)consts, log2n, s, last, butterflies);
     }
     BBG_HIP(hipGetLastError());
     return BBG_OK;
@@ -173,17 +179,28 @@ static int ecntt_stages_upto(bbg_ctx* ctx, void* d_work, unsigned log2n, int inv
 // w_n^-1 and n^-1, else with w_n and no scaling.
 int ecntt_stages(bbg_ctx* ctx, void* d_work, unsigned log2n, int inverse, hipStream_t st)
 {
-    return ecntt_stages_upto(ctx, d_work, log2n, inverse, log2n, st);
+    return ecntt_stages_upto(ctx, d_work, log2n, 1, inverse, log2n, st);
 }
 
 // 2^(log2n - log2block) independent FORWARD transforms of 2^log2block points each, in place on the contiguous blocks of d_work (each
 // bit-reversed within itself): the first log2block stages of the schedule over the whole array.  Stage s takes w_2m^j, m = 2^s, whatever
 // the array length -- the stage kernels rebuild it from the 2^log2n domain's table as j << (log2n - 1 - s).  The inverse folds n^-1 into
-// its last stage and has no such form.
+// its last stage and has no such form: ecntt_stages_batch below is the one for it.
 int ecntt_stages_blocks(bbg_ctx* ctx, void* d_work, unsigned log2n, unsigned log2block, hipStream_t st)
 {
     if (log2block < 1 || log2block > log2n) { set_error("ecntt: block size out of range"); return BBG_E_INVALID; }
-    return ecntt_stages_upto(ctx, d_work, log2n, 0, log2block, st);
+    return ecntt_stages_upto(ctx, d_work, log2n, 1, 0, log2block, st);
+}
+
+// `count` independent transforms of 2^log2block points each, any count >= 1, in EITHER direction, in place on the contiguous blocks of
+// d_work (each bit-reversed within itself, natural order afterwards): ALL log2block stages of the 2^log2block domain with the butterfly
+// index running to count 2^(log2block - 1).  Butterfly t has j = t mod m and i = (t / m) 2m + j: t / m runs through the pairs of one
+// block and on into the next, since a block is a whole number of pairs at every stage, and the twiddle is w_2m^(+-j) whatever the block.
+// The last stage is the domain's last, so the inverse's n^-1 is that of 2^log2block.  One launch per stage whatever the count.
+int ecntt_stages_batch(bbg_ctx* ctx, void* d_work, unsigned log2block, size_t count, int inverse, hipStream_t st)
+{
+    if (count == 0 || count > ((size_t)1 << 40)) { set_error("ecntt: batch count out of range"); return BBG_E_INVALID; }
+    return ecntt_stages_upto(ctx, d_work, log2block, count, inverse, log2block, st);
 }
 
 // d_out[i] = d_work[i] as canonical affine on `st`, n points.  d_inf_flag != null: a point at infinity sets *d_inf_flag (cleared by the

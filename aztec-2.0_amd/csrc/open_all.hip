@@ -54,6 +54,7 @@
 #include "bbg_internal.h"
 #include "curve.hip.h"
 #include "ecntt.hip.h" // bit_reverse
+#include "ntt_consts.hip.h" // DomainConsts, pow_from_table
 #include "var_base.hip.h"
 
 namespace bbg {
@@ -68,15 +69,18 @@ __global__ void __launch_bounds__(256) k_open_all_srs(const Affine* __restrict__
 }
 
 // c^[0] = f_(n-1), c^[n+1+i] = f_i for i = 1 .. n-2, zero elsewhere, 2n entries.  The words are copied as they come (any representative).
-__global__ void __launch_bounds__(256) k_open_all_coeffs(const Fr* __restrict__ f, Fr* __restrict__ c_hat, unsigned log2n)
+// `count` polynomials at f + p n give c^ at c_hat + p 2n: item g is entry g mod 2n of polynomial g / 2n.
+__global__ void __launch_bounds__(256) k_open_all_coeffs(const Fr* __restrict__ f, Fr* __restrict__ c_hat, unsigned log2n, size_t count)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t n = (size_t)1 << log2n;
-    if (i >= 2 * n) return;
+    if (g >= count * 2 * n) return;
+    const size_t i = g & (2 * n - 1);
+    const Fr* fp = f + ((g >> (log2n + 1)) << log2n);
     Fr v = Fr::zero();
-    if (i == 0) v = fe_load<FrP>(f + (n - 1));
-    else if (i >= n + 2) v = fe_load<FrP>(f + (i - n - 1));
-    fe_store<FrP>(c_hat + i, v);
+    if (i == 0) v = fe_load<FrP>(fp + (n - 1));
+    else if (i >= n + 2) v = fe_load<FrP>(fp + (i - n - 1));
+    fe_store<FrP>(c_hat + g, v);
 }
 
 // work[bitrev(i)] = c_hat[i] * s_hat[i], i < 2^log2m.  Two waves per SIMD, no LDS, no scratch (the register budget of k_ecntt_stage_glv,
@@ -96,12 +100,33 @@ __global__ void __launch_bounds__(64, 2) k_open_all_pointwise(const Affine* __re
     }
 }
 
-// dst[i] = src[bitrev(i)], i < 2^log2n: the first half of the 2n results as the input of the size-n transform
-__global__ void __launch_bounds__(256) k_open_all_fold(const Xyzz* __restrict__ src, Xyzz* __restrict__ dst, unsigned log2n)
+// The products of `count` polynomials in one launch: work[p 2^log2m + bitrev(i)] = c_hat[p 2^log2m + i] * s_hat[i] for the items
+// g = p 2^log2m + i < items = count 2^log2m.  s_hat is indexed by i alone and the destination is the single call's, within polynomial
+// p's array.  The loop body, launch shape and register budget of k_open_all_pointwise; a lane's items may lie in different polynomials.
+__global__ void __launch_bounds__(64, 2) k_open_batch_pointwise(const Affine* __restrict__ s_hat, const Fr* __restrict__ c_hat, Xyzz* __restrict__ work, unsigned log2m,
+                                                                size_t items, Xyzz* __restrict__ tables)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ((size_t)1 << log2n)) return;
-    xyzz_store(dst + i, xyzz_load(src + bit_reverse(i, log2n)));
+    const size_t lanes = (size_t)gridDim.x * blockDim.x;
+    const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    Xyzz* table = tables + (size_t)blockIdx.x * 64 * GLV_TABLE; // the wave's 64 tables (blocks of one wave): wave-uniform
+#pragma unroll 1
+    for (size_t g = lane; g < items; g += lanes) {
+        const size_t i = g & (((size_t)1 << log2m) - 1);
+        const Affine a = aff_load(s_hat + i);
+        const Xyzz p = aff_is_inf(a) ? xyzz_inf() : xyzz_from_affine(a);
+        const Fr k = fe_reduce_once(fe_from_mont(fe_load<FrP>(c_hat + g)));
+        xyzz_store(work + (g - i) + bit_reverse(i, log2m), xyzz_mul_glv(p, k, table));
+    }
+}
+
+// dst[p n + i] = src[p 2n + bitrev(i)], i < n = 2^log2n, p < count: the first half of each polynomial's 2n results as the input of its
+// size-n transform
+__global__ void __launch_bounds__(256) k_open_all_fold(const Xyzz* __restrict__ src, Xyzz* __restrict__ dst, unsigned log2n, size_t count)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (count << log2n)) return;
+    const size_t i = g & (((size_t)1 << log2n) - 1);
+    xyzz_store(dst + g, xyzz_load(src + ((g - i) << 1) + bit_reverse(i, log2n)));
 }
 
 // cells: src[k l + c] = s^(b)[k] with b = bitrev_l(c), k < 2r: s_(l (r-2-k) + b) for k <= r-2, aff_inf() above.  2n entries; log2cell >= 1.
@@ -115,17 +140,73 @@ __global__ void __launch_bounds__(256) k_open_cells_srs(const Affine* __restrict
 }
 
 // cells: c_hat[b 2r + i] = c^(b)[i]: f_(l (r-1) + b) at i = 0, f_(l (i-r-1) + b) for i = r+2 .. 2r-1, zero elsewhere.  2n entries, the
-// words copied as they come.
-__global__ void __launch_bounds__(256) k_open_cells_coeffs(const Fr* __restrict__ f, Fr* __restrict__ c_hat, unsigned log2n, unsigned log2cell)
+// words copied as they come.  `count` polynomials at f + p n give theirs at c_hat + p 2n: item g is entry g mod 2n of polynomial g / 2n.
+__global__ void __launch_bounds__(256) k_open_cells_coeffs(const Fr* __restrict__ f, Fr* __restrict__ c_hat, unsigned log2n, unsigned log2cell, size_t count)
 {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t n = (size_t)1 << log2n, r = n >> log2cell;
-    if (j >= 2 * n) return;
+    if (g >= count * 2 * n) return;
+    const size_t j = g & (2 * n - 1);
+    const Fr* fp = f + ((g >> (log2n + 1)) << log2n);
     const size_t b = j >> (log2n - log2cell + 1), i = j & (2 * r - 1);
     Fr v = Fr::zero();
-    if (i == 0) v = fe_load<FrP>(f + (((r - 1) << log2cell) + b));
-    else if (i >= r + 2) v = fe_load<FrP>(f + (((i - r - 1) << log2cell) + b));
-    fe_store<FrP>(c_hat + j, v);
+    if (i == 0) v = fe_load<FrP>(fp + (((r - 1) << log2cell) + b));
+    else if (i >= r + 2) v = fe_load<FrP>(fp + (((i - r - 1) << log2cell) + b));
+    fe_store<FrP>(c_hat + g, v);
+}
+
+// The Fr transforms of a batched call, one per workgroup, in LDS.  Workgroup blockIdx.x = p l + b builds block b of polynomial p's c^
+// vectors as it loads it (the scatter of k_open_cells_coeffs; k_open_all_coeffs' for log2cell = 0, where b = 0 and 2r = 2n), bit-reversed,
+// runs the log2(2r) radix-2 stages of the decimation-in-time schedule with a barrier after each, and writes c_hat[(p l + b) 2r + i] in
+// natural order: what ntt_run(BBG_FFT) leaves there up to the representative in [0, 2r), which the products reduce away.  2r x 32 B of
+// dynamic LDS as two planes of 16 B words (ds_read_b128 / ds_write_b128 on consecutive addresses); w_2m^j from the 2r domain's table of
+// root^(2^b), at most log2(2r) - 1 products per butterfly.  2r >= 4; the host takes this kernel up to 2r = 2^OPEN_BATCH_LDS_LOG2.
+constexpr unsigned OPEN_BATCH_LDS_LOG2 = 12; // 2^12 x 32 B = 128 KiB of a CU's 160 KiB: one workgroup per CU there, two at 2^11
+__device__ __forceinline__ Fr lds_fr_load(const uint4* lo, const uint4* hi, unsigned i)
+{
+    const uint4 a = lo[i], b = hi[i];
+    Fr r;
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
+    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
+    return r;
+}
+__device__ __forceinline__ void lds_fr_store(uint4* lo, uint4* hi, unsigned i, const Fr& x)
+{
+    lo[i] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+    hi[i] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+}
+__global__ void __launch_bounds__(256) k_open_batch_ntt_lds(const Fr* __restrict__ f, Fr* __restrict__ c_hat, const DomainConsts* __restrict__ dc, unsigned log2n,
+                                                            unsigned log2cell)
+{
+    extern __shared__ uint4 lds[];
+    const unsigned log2b = log2n - log2cell + 1;
+    const unsigned len = 1u << log2b, r = len >> 1;
+    uint4* lo = lds;
+    uint4* hi = lds + len;
+    const size_t b = blockIdx.x & ((1u << log2cell) - 1);
+    const Fr* fp = f + ((size_t)(blockIdx.x >> log2cell) << log2n);
+    for (unsigned i = threadIdx.x; i < len; i += blockDim.x) {
+        Fr v = Fr::zero();
+        if (i == 0) v = fe_load<FrP>(fp + (((size_t)(r - 1) << log2cell) + b));
+        else if (i >= r + 2) v = fe_load<FrP>(fp + (((size_t)(i - r - 1) << log2cell) + b));
+        lds_fr_store(lo, hi, (unsigned)bit_reverse(i, log2b), v);
+    }
+    __syncthreads();
+    for (unsigned s = 0; s < log2b; s++) {
+        const unsigned m = 1u << s;
+        for (unsigned t = threadIdx.x; t < r; t += blockDim.x) {
+            const unsigned j = t & (m - 1);
+            const unsigned i = ((t >> s) << (s + 1)) + j;
+            const Fr a = lds_fr_load(lo, hi, i);
+            Fr x = lds_fr_load(lo, hi, i + m);
+            if (j != 0) x = fe_mul(x, pow_from_table(dc->pow2_root, (uint64_t)j << (log2b - 1 - s))); // w_2m^j = w_2r^(j 2r / 2m)
+            lds_fr_store(lo, hi, i, fe_add(a, x));
+            lds_fr_store(lo, hi, i + m, fe_sub(a, x));
+        }
+        __syncthreads();
+    }
+    Fr* out = c_hat + ((size_t)blockIdx.x << log2b);
+    for (unsigned i = threadIdx.x; i < len; i += blockDim.x) fe_store<FrP>(out + i, lds_fr_load(lo, hi, i));
 }
 
 // cells: dst[k] = sum_(t < 2^log2cell) src[k 2^log2cell + t], k < count.  One thread per output, its entries added one after the other by
@@ -157,6 +238,7 @@ void open_all_release(struct bbg_open_all* h)
     if (h->work1) (void)hipFree(h->work1);
     if (h->sum) (void)hipFree(h->sum);
     if (h->c_hat) (void)hipFree(h->c_hat);
+    if (h->batch_ws) (void)hipFree(h->batch_ws);
     delete h;
 }
 
@@ -242,7 +324,7 @@ static int open_cells_run(struct bbg_open_all* h, const void* d_coeffs, void* d_
     if (rc) return rc;
     {
         ProfScope ps(ctx, "open_all_coeffs", st);
-        hipLaunchKernelGGL(k_open_cells_coeffs, dim3(grid_for(m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, (Fr*)h->c_hat, log2n, log2cell);
+        hipLaunchKernelGGL(k_open_cells_coeffs, dim3(grid_for(m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, (Fr*)h->c_hat, log2n, log2cell, (size_t)1);
     }
     for (size_t b = 0; b < ((size_t)1 << log2cell); b++) {
         rc = ntt_run(ctx, (Fr*)h->c_hat + b * 2 * r, log2r + 1, BBG_FFT, 0, nullptr, st);
@@ -264,7 +346,7 @@ static int open_cells_run(struct bbg_open_all* h, const void* d_coeffs, void* d_
     }
     {
         ProfScope ps(ctx, "open_all_fold", st);
-        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(r, 256)), dim3(256), 0, st, (const Xyzz*)h->sum, (Xyzz*)h->work1, log2r);
+        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(r, 256)), dim3(256), 0, st, (const Xyzz*)h->sum, (Xyzz*)h->work1, log2r, (size_t)1);
     }
     {
         ProfScope ps(ctx, "ecntt_stages", st);
@@ -291,7 +373,7 @@ int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipS
     if (rc) return rc;
     {
         ProfScope ps(ctx, "open_all_coeffs", st);
-        hipLaunchKernelGGL(k_open_all_coeffs, dim3(grid_for(m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, (Fr*)h->c_hat, log2n);
+        hipLaunchKernelGGL(k_open_all_coeffs, dim3(grid_for(m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, (Fr*)h->c_hat, log2n, (size_t)1);
     }
     rc = ntt_run(ctx, h->c_hat, log2m, BBG_FFT, 0, nullptr, st);
     if (rc) return rc;
@@ -307,7 +389,7 @@ int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipS
     }
     {
         ProfScope ps(ctx, "open_all_fold", st);
-        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Xyzz*)h->work2, (Xyzz*)h->work1, log2n);
+        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(n, 256)), dim3(256), 0, st, (const Xyzz*)h->work2, (Xyzz*)h->work1, log2n, (size_t)1);
     }
     {
         ProfScope ps(ctx, "ecntt_stages", st);
@@ -317,6 +399,138 @@ int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipS
     rc = ecntt_normalize(ctx, h->work1, n, d_out, nullptr, st);
     if (rc) return rc;
     BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- many polynomials per call
+// A single call is latency: its G1 stages are dependent launches over 2r and r points that leave the chip idle.  A batched call runs the
+// same number of launches over c polynomials each.  Its working arrays are c copies of the single call's, polynomial-major, in one
+// allocation the handle owns; c is at most what OPEN_BATCH_BUDGET holds, and a call walks its polynomials in chunks of c.
+constexpr size_t OPEN_BATCH_BUDGET = (size_t)1 << 30;
+static_assert(sizeof(Xyzz) == 128 && sizeof(Fr) == 32, "the workspace is laid out in 128 B points and 32 B scalars");
+
+// the working arrays of one polynomial: what the handle holds beside s_hat
+size_t open_all_batch_poly_bytes(unsigned log2n, unsigned log2cell)
+{
+    return open_all_bytes(log2n, log2cell) - (((size_t)2 << log2n) * 64);
+}
+
+size_t open_all_batch_cap(unsigned log2n, unsigned log2cell)
+{
+    return std::max<size_t>(1, OPEN_BATCH_BUDGET / open_all_batch_poly_bytes(log2n, log2cell));
+}
+
+// the workspace for min(polys, the cap) polynomials; 0 releases it.  Replacing one waits for the device: queued calls may still use it.
+int open_all_batch_reserve(struct bbg_open_all* h, size_t polys)
+{
+    polys = std::min(polys, open_all_batch_cap(h->log2n, h->log2cell));
+    if (polys == h->batch_cap) return BBG_OK;
+    if (h->batch_ws) {
+        BBG_HIP(hipDeviceSynchronize());
+        void* old = h->batch_ws;
+        h->batch_ws = nullptr;
+        h->batch_cap = 0;
+        BBG_HIP(hipFree(old));
+    }
+    if (polys == 0) return BBG_OK;
+    hipError_t e = hipMalloc(&h->batch_ws, polys * open_all_batch_poly_bytes(h->log2n, h->log2cell));
+    if (e != hipSuccess) {
+        h->batch_ws = nullptr;
+        (void)hipGetLastError(); // the handle stays usable: a single call ends in a hipGetLastError of its own
+        return hip_fail(e, "bbg_open_all_batch_reserve: the workspace", __FILE__, __LINE__);
+    }
+    h->batch_cap = polys;
+    return BBG_OK;
+}
+
+// c <= batch_cap polynomials at d_coeffs, c x proofs points to d_out.  Queues only.
+static int open_batch_chunk(struct bbg_open_all* h, const void* d_coeffs, size_t c, void* d_out, hipStream_t st)
+{
+    bbg_ctx* ctx = h->ctx;
+    const unsigned log2n = h->log2n, log2cell = h->log2cell, log2m = log2n + 1;
+    const unsigned log2p = log2n - log2cell;       // proofs per polynomial: the forward transform's size (r; n for all points)
+    const unsigned log2b = log2p + 1;              // the Fr transforms' and the inverse transform's size (2r; 2n)
+    const size_t m = (size_t)1 << log2m, proofs = (size_t)1 << log2p, cap = h->batch_cap;
+    // the workspace: work2 | work1 | sum | c_hat, each for `cap` polynomials
+    char* ws = (char*)h->batch_ws;
+    Xyzz* work2 = (Xyzz*)ws;
+    Xyzz* work1 = work2 + cap * m;
+    Xyzz* sum = work1 + cap * proofs;
+    Fr* c_hat = (Fr*)(sum + (log2cell ? cap * 2 * proofs : 0));
+    Xyzz* inv = log2cell ? sum : work2; // the inverse transforms' arrays
+    // the largest table set of the call first, as in open_all_run
+    size_t lanes = 0;
+    void* tables = nullptr;
+    int rc = var_base_tables(ctx, c * m, &lanes, &tables);
+    if (rc) return rc;
+    if (log2b <= OPEN_BATCH_LDS_LOG2) { // c l transforms of 2r points, one workgroup each, the scatter fused into the load
+        void* consts = nullptr;
+        rc = ntt_domain_consts(ctx, log2b, &consts);
+        if (rc) return rc;
+        const size_t lds_bytes = ((size_t)1 << log2b) * 32;
+        if (lds_bytes > 64 * 1024 && !h->batch_lds_attr) {
+            BBG_HIP(hipFuncSetAttribute((const void*)k_open_batch_ntt_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)1 << OPEN_BATCH_LDS_LOG2) * 32)));
+            h->batch_lds_attr = true;
+        }
+        ProfScope ps(ctx, "ntt_pass", st);
+        hipLaunchKernelGGL(k_open_batch_ntt_lds, dim3((unsigned)(c << log2cell)), dim3(256), lds_bytes, st, (const Fr*)d_coeffs, c_hat, (const DomainConsts*)consts, log2n,
+                           log2cell);
+    } else { // 2r x 32 B does not fit a workgroup's LDS: the scatter in one launch, then the single call's transforms block by block
+        {
+            ProfScope ps(ctx, "open_all_coeffs", st);
+            if (log2cell)
+                hipLaunchKernelGGL(k_open_cells_coeffs, dim3(grid_for(c * m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, c_hat, log2n, log2cell, c);
+            else
+                hipLaunchKernelGGL(k_open_all_coeffs, dim3(grid_for(c * m, 256)), dim3(256), 0, st, (const Fr*)d_coeffs, c_hat, log2n, c);
+        }
+        for (size_t t = 0; t < (c << log2cell); t++) {
+            rc = ntt_run(ctx, c_hat + (t << log2b), log2b, BBG_FFT, 0, nullptr, st);
+            if (rc) return rc;
+        }
+    }
+    {
+        ProfScope ps(ctx, "open_all_pointwise", st);
+        hipLaunchKernelGGL(k_open_batch_pointwise, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (const Affine*)h->s_hat, (const Fr*)c_hat, work2, log2m, c * m,
+                           (Xyzz*)tables);
+    }
+    if (log2cell) {
+        ProfScope ps(ctx, "open_cells_sum", st);
+        hipLaunchKernelGGL(k_open_cells_sum, dim3(grid_for(c * 2 * proofs, 64)), dim3(64), 0, st, (const Xyzz*)work2, sum, c * 2 * proofs, log2cell);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        rc = ecntt_stages_batch(ctx, inv, log2b, c, 1, st);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(ctx, "open_all_fold", st);
+        hipLaunchKernelGGL(k_open_all_fold, dim3(grid_for(c * proofs, 256)), dim3(256), 0, st, (const Xyzz*)inv, work1, log2p, c);
+    }
+    {
+        ProfScope ps(ctx, "ecntt_stages", st);
+        rc = ecntt_stages_batch(ctx, work1, log2p, c, 0, st);
+        if (rc) return rc;
+    }
+    rc = ecntt_normalize(ctx, work1, c * proofs, d_out, nullptr, st);
+    if (rc) return rc;
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+// d_coeffs: count x 2^log2n Montgomery Fr, polynomial-major (read only); d_out: count x proofs x 64 B.  A handle without a reservation
+// reserves min(count, the cap) first.  Queues only.
+int open_all_batch_run(struct bbg_open_all* h, const void* d_coeffs, size_t count, void* d_out, hipStream_t st)
+{
+    if (!h->batch_cap) {
+        int rc = open_all_batch_reserve(h, count);
+        if (rc) return rc;
+    }
+    const size_t n = (size_t)1 << h->log2n, proofs = n >> h->log2cell;
+    for (size_t done = 0; done < count; done += h->batch_cap) {
+        const size_t c = std::min(h->batch_cap, count - done);
+        int rc = open_batch_chunk(h, (const char*)d_coeffs + done * n * 32, c, (char*)d_out + done * proofs * 64, st);
+        if (rc) return rc;
+    }
     return BBG_OK;
 }
 

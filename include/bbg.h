@@ -231,6 +231,23 @@ int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs);
 int bbg_open_all_device(struct bbg_open_all* h, const void* d_coeffs, void* d_out_affine);
 /* Host arrays; returns when the proofs are in out_affine. */
 int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_affine);
+/* Many polynomials per call, on either kind of handle.  One call of bbg_open_all_device is a chain of dependent G1 stages over few points
+ * (13 launches at (log2n, log2cell) = (12, 6)) and leaves the device idle; the batched call runs the same chain once over `count`
+ * polynomials.  out[p] is, bit for bit, what bbg_open_all writes for polynomial p alone.
+ * bbg_open_all_batch_reserve: the handle's batch workspace for `polys` polynomials at a time -- `polys` copies of the single call's working
+ * arrays (bbg_open_all_device_bytes less the 2n x 64 B of transformed points, each), owned by the handle beside the buffers of the single
+ * calls, which keep theirs.  `polys` above the cap -- the largest number whose workspace stays within 1 GiB, at least 1 -- reserves the
+ * cap; 0 releases the workspace.  Replacing or releasing a reservation waits for the device.  BBG_E_NOMEM when the allocation fails: the
+ * handle then has no reservation and still serves single calls.
+ * bbg_open_all_batch_device: d_coeffs = count x 2^log2n Montgomery Fr (any representative in [0, 2r)), polynomial p at p * 2^log2n, read
+ * only; d_out_affine = count x proofs x 64 B canonical Montgomery affine, polynomial-major, proofs = bbg_open_all_count.  The call walks
+ * its polynomials in chunks of the reservation; on a handle without one it first reserves min(count, the cap).  Asynchronous on the
+ * context stream, no host synchronisation (but for that first reservation's allocation).  Timed under the names of bbg_open_all_device;
+ * "ntt_pass" covers the batched Fr transforms.  A null pointer or count = 0 is BBG_E_INVALID. */
+int bbg_open_all_batch_reserve(struct bbg_open_all* h, size_t polys);
+int bbg_open_all_batch_device(struct bbg_open_all* h, const void* d_coeffs, size_t count, void* d_out_affine);
+/* Host arrays; returns when the count x proofs proofs are in out_affine. */
+int bbg_open_all_batch(struct bbg_open_all* h, const uint64_t* coeffs, size_t count, uint64_t* out_affine);
 
 /* ---- cells as data: the values of every cell of a polynomial, and the polynomial back from a subset of its cells (erasure decoding; the
  *      consumer side of the cell handle above, pure Fr work).  n = 2^log2n, l = 2^log2cell, r = n / l, cell m < r = { w_n^(m + r t) : t < l }.
@@ -291,6 +308,8 @@ int bbg_cells_verify_reduce_device(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, u
 int bbg_cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const uint64_t* commitments, size_t ncom,
                             const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const uint64_t* values, const uint64_t* proofs,
                             const uint64_t rho[4], uint64_t out[16]);
+/* The handle's device memory: its own buffers plus the batch workspace it holds at the moment (none before the first reservation or
+ * batched call, and none after bbg_open_all_batch_reserve(h, 0)). */
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes);
 /* Releases the handle and its device memory (a device synchronisation); must precede bbg_destroy of its context. */
 void bbg_open_all_free(struct bbg_open_all* h);
