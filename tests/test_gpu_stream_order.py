@@ -20,67 +20,52 @@ missing device-side wait.
 Expected values come from the C oracle on the same inputs (pippenger, msm_naive, g1_sum, g1_mul, ntt, poly_binop), compared bit for bit
 as canonical Montgomery affine points / canonical field elements.  No result of the library is used as an expectation.
 
-Nothing here asserts the negative ("without a join the snapshot is stale"): that is a race, not a property."""
-import contextlib
+Nothing here asserts the negative ("without a join the snapshot is stale"): that is a race, not a property.
 
+The helpers of a section (`env`, `options`, `unsynchronised`, ..) live in tests/tools/stream_order.py and serve this file and its second
+half, tests/test_gpu_stream_order_device.py ("device:" below; A / B / C n are the sections of that file, B = the inputs zeroed on the stream
+right behind the call).  Every *_device function declared in include/bbg.h, and the case that covers it:
+
+  bbg_msm_device                         sections 1 - 5, 7, 8 here; device: C 2 (beside a reduction that shares the arena)
+  bbg_msm_batch_device                   sections 5, 6
+  bbg_g1_sum_device                      section 7
+  bbg_ntt_device                         section 9; device: C 1 (the filler in front of the pinned-array calls)
+  bbg_poly_op_device                     section 9
+  bbg_g1_fixed_base_mul_device           section 9; device: C 3 (the one table slot rebuilt twice)
+  bbg_g1_batch_mul_device                section 9; device: C 4
+  bbg_g1_ntt_device                      device: A 1 (both directions, ecntt_mul 1 and 0), B 1, C 4
+  bbg_open_all_device                    device: A 2 (every point, 2^8), A 3 / B 3 (cells, (10, 4)), C 4, C 5 (behind a stream switch)
+  bbg_open_all_batch_device              device: A 4 / B 4 (chunks of 2, 2, 1 over one workspace; one chunk of 3)
+  bbg_cells_values_device                device: A 5
+  bbg_cells_recover_device               device: A 6 / B 6, C 1
+  bbg_cells_verify_reduce_device         device: A 7 / B 7 (msm_async_reduce 0 and 1), C 1, C 2
+  bbg_fr_batch_invert_device             device: A 8
+  bbg_kate_opening_device                device: A 9 (synchronises for F(z); the quotient array is snapshotted on the stream)
+  bbg_kate_opening_lagrange_device       device: A 9 (the same)
+  bbg_poly_linear_combination_device     device: A 10 (poly_limbs29 1 and 0)
+  bbg_permutation_grand_product_device   device: A 11
+  bbg_quotient_widget_device             device: A 12 (alpha_base_out = NULL: with it the call synchronises)
+  bbg_divide_by_pseudo_vanishing_device  device: A 13
+  bbg_cross_dft_device                   device: A 14
+  bbg_scale_powers_device                device: A 15
+  bbg_coset_fft_split_device             device: A 16
+  bbg_poly_evaluate_device               none: its only output is a host value, returned after the call's own synchronisation
+  bbg_poly_evaluate_lagrange_device      none: the same
+  bbg_srs_register_device                none: it queues the table build on the context stream and synchronises it before it returns its
+                                         only output, the handle
+  bbg_multi_ntt_device                   none, for another reason than the three above: it runs on the streams of the group's own contexts
+                                         and its contract is completion after bbg_multi_sync, not the order of a caller's stream.
+                                         tests/test_gpu_parity.py::test_multi_ntt_all_to_all reads the shards behind bbg_multi_sync, but through
+                                         a blocking download, so NO test shows that bbg_multi_sync alone completes them: that gap is open"""
 import numpy as np
 import pytest
 
 import lagrange_model as lm
+from stream_order import N16, N_TINY, SEED_K, affine, env, options, poisoned, to_device, unsynchronised, words  # noqa: F401 (env: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-SRS_SEED = 0xBB254
-N16 = 1 << 16
-N_TINY = 4096  # the 8-bit-window path of csrc/msm_tiny.hip, which has its own copy of the slot and event code
-POISON = 0x5A
-SEED_A, SEED_B, SEED_C, SEED_T, SEED_U, SEED_K = 0x57A0, 0x57A1, 0x57A2, 0x57A3, 0x57A4, 0x57A5
-DEFAULTS = {"msm_async_reduce": 0, "msm_window": 0}
-
-
-class Env:
-    pass
-
-
-@pytest.fixture(scope="module")
-def env(pkg, oracle):
-    """A context of its own on an ordinary non-blocking torch stream (the session-wide `bbg` fixture stays on torch's current stream), a
-    hashed SRS of 2^16 points and its points for the oracle."""
-    import torch
-    e = Env()
-    e.torch, e.pkg, e.oracle = torch, pkg, oracle
-    e.ctx = pkg.Bbg(0)
-    e.s = torch.cuda.Stream()
-    assert e.s.cuda_stream != 0, "torch.cuda.Stream() must be a stream of its own, not the null stream"
-    e.ctx.set_stream(e.s.cuda_stream)
-    e.srs = e.ctx.srs_synth_hashed(SRS_SEED, N16)
-    e.pts = e.srs.read()
-    e.want = {}
-    # The automatic width of a short MSM over a long SRS is the nearest width that already has window tables (msm_choose in csrc/msm.hip),
-    # so the 8-bit tables are built once here: from then on 4096 and 1000 terms take msm_tiny.hip at the automatic width.
-    e.ctx.set_option("msm_window", 8)
-    try:
-        e.ctx.msm(e.srs, pkg.synthetic_scalars(SEED_K, 64))
-    finally:
-        e.ctx.set_option("msm_window", 0)
-    assert e.ctx.msm_plan(N_TINY, e.srs)[0] == 8 and e.ctx.msm_plan(1000, e.srs)[0] == 8
-    assert e.ctx.msm_plan(N16, e.srs)[0] == 16
-    yield e
-    e.ctx.sync()
-    e.srs.free()
-    e.ctx.close()
-
-
-@contextlib.contextmanager
-def options(env, **kv):
-    """Options are set before an unsynchronised section and restored after it ("msm_async_reduce" synchronises the device)."""
-    for k, v in kv.items():
-        env.ctx.set_option(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            env.ctx.set_option(k, DEFAULTS[k])
+SEED_A, SEED_B, SEED_C, SEED_T, SEED_U = 0x57A0, 0x57A1, 0x57A2, 0x57A3, 0x57A4
 
 
 def scalars(env, seed, n):
@@ -96,44 +81,6 @@ def want_msm(env, seed, n, start=0, naive=False):
         r.setflags(write=False)
         env.want[key] = r
     return env.want[key]
-
-
-def to_device(env, a):
-    with env.torch.cuda.stream(env.s):
-        return env.torch.from_numpy(np.ascontiguousarray(a).view(np.int64).reshape(-1)).cuda()
-
-
-def poisoned(env, nbytes):
-    return env.torch.full((nbytes,), POISON, dtype=env.torch.uint8, device="cuda")
-
-
-def affine(env, snap):
-    """Host bytes of k Jacobian results -> (k, 8) canonical affine points."""
-    j = np.ascontiguousarray(snap).view(np.uint64).reshape(-1, 12)
-    return np.stack([env.oracle.jac_to_affine(p) for p in j])
-
-
-def words(snap, last):
-    return np.ascontiguousarray(snap).view(np.uint64).reshape(-1, last)
-
-
-def unsynchronised(env, masters, out_bytes, body, between=None, final_stream=None):
-    """Runs body(inputs, outs) -> [snapshot tensors] on the context's stream: once into scratch buffers (first-use work, see the module
-    docstring), then -- after a full synchronisation and the optional `between()` -- on poisoned result tensors; returns the snapshots as
-    host arrays.  inputs: fresh device copies of `masters` per pass (a body may overwrite them); outs: one poisoned uint8 tensor per entry
-    of out_bytes.  body must not synchronise the host; the only synchronisation after it is the stream's own."""
-    torch = env.torch
-    with torch.cuda.stream(env.s):
-        body([m.clone() for m in masters], [poisoned(env, b) for b in out_bytes])
-        env.ctx.sync()
-        torch.cuda.synchronize()
-        if between is not None:
-            between()
-        inputs = [m.clone() for m in masters]
-        outs = [poisoned(env, b) for b in out_bytes]  # step 1
-        snaps = body(inputs, outs)                    # steps 2 - 4
-        (final_stream or env.s).synchronize()         # step 5
-        return [t.cpu().numpy() for t in snaps]
 
 
 def msm(env, d_scalars, n, out, start=0, scalar_offset=0, out_offset=0):
