@@ -55,8 +55,9 @@ right behind the call).  Every *_device function declared in include/bbg.h, and 
                                          only output, the handle
   bbg_multi_ntt_device                   none, for another reason than the three above: it runs on the streams of the group's own contexts
                                          and its contract is completion after bbg_multi_sync, not the order of a caller's stream.
-                                         tests/test_gpu_parity.py::test_multi_ntt_all_to_all reads the shards behind bbg_multi_sync, but through
-                                         a blocking download, so NO test shows that bbg_multi_sync alone completes them: that gap is open"""
+                                         tests/test_gpu_multi_group.py::test_multi_sync_alone_completes_a_resident_call shows that with this
+                                         file's discipline (snapshots on fresh streams behind bbg_multi_sync, nothing else synchronised); its
+                                         back-to-back sections queue group calls with no synchronisation between them"""
 import numpy as np
 import pytest
 
