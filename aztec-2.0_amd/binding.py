@@ -88,6 +88,9 @@ def load_library():
         "bbg_g1_batch_mul": (cint, [vp, vp, vp, sz, cint, vp]),
         "bbg_g1_batch_mul_device": (cint, [vp, vp, vp, sz, cint, vp]),
         "bbg_srs_scale_powers": (cint, [vp, vp, vp, ctypes.POINTER(vp)]),
+        "bbg_g1_msm": (cint, [vp, vp, vp, sz, cint, vp]),
+        "bbg_g1_msm_device": (cint, [vp, vp, vp, sz, cint, vp]),
+        "bbg_g1_msm_plan": (cint, [sz, cint, ctypes.POINTER(cint), ctypes.POINTER(cint), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "bbg_g1_ntt": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_g1_ntt_device": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_open_all_prepare": (cint, [vp, vp, ctypes.c_uint, ctypes.POINTER(vp)]),
@@ -197,6 +200,7 @@ EXPORTED_SYMBOLS = [
     "bbg_open_all_batch_reserve", "bbg_open_all_batch_device", "bbg_open_all_batch",
     "bbg_cells_values_device", "bbg_cells_values", "bbg_cells_recover_device", "bbg_cells_recover",
     "bbg_cells_verify_reduce_device", "bbg_cells_verify_reduce",
+    "bbg_g1_msm", "bbg_g1_msm_device", "bbg_g1_msm_plan",
 ]
 
 
@@ -479,6 +483,30 @@ class Bbg:
     def g1_batch_mul_device(self, d_points, d_scalars, n, d_out, one_scalar=False):
         self._ck(self.lib.bbg_g1_batch_mul_device(self.ctx, ctypes.c_void_p(d_points), ctypes.c_void_p(d_scalars), n, int(bool(one_scalar)),
                                                   ctypes.c_void_p(d_out)))
+
+    def g1_msm(self, points, scalars, window_bits=0):
+        """sum_i scalars[i] * points[i] over plain (n, 8) affine points, no SRS: one canonical affine point (8 limbs), the affine encoding
+        of infinity for an infinite sum and for n = 0; window_bits 0 = automatic, else 2 .. 16 (bbg_g1_msm)."""
+        pt, sc = _u64(points, 8), _u64(scalars, 4)
+        if sc.shape[0] != pt.shape[0]:
+            raise ValueError("one scalar per point")
+        out = np.zeros(8, dtype=np.uint64)
+        self._ck(self.lib.bbg_g1_msm(self.ctx, pt.ctypes.data, sc.ctypes.data, pt.shape[0], int(window_bits), out.ctypes.data))
+        return out
+
+    def g1_msm_device(self, d_points, d_scalars, n, d_out, window_bits=0):
+        """Device pointers, 64 bytes at d_out; asynchronous (bbg_g1_msm_device)."""
+        self._ck(self.lib.bbg_g1_msm_device(self.ctx, ctypes.c_void_p(d_points), ctypes.c_void_p(d_scalars), n, int(window_bits), ctypes.c_void_p(d_out)))
+
+    @staticmethod
+    def g1_msm_plan(n, window_bits=0):
+        """(c, windows, chunk_terms, segment_entries) of a bbg_g1_msm call with these arguments; needs no device and no context
+        (bbg_g1_msm_plan)."""
+        c, windows, chunk, seg = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+        lib = load_library()
+        if lib.bbg_g1_msm_plan(n, int(window_bits), ctypes.byref(c), ctypes.byref(windows), ctypes.byref(chunk), ctypes.byref(seg)) != 0:
+            raise BbgError(lib.bbg_last_error().decode())
+        return c.value, windows.value, chunk.value, seg.value
 
     def g1_ntt(self, points, inverse=False):
         """The NTT over G1 of (n, 8) affine points, n a power of two >= 2: out[k] = sum_j w^(jk) P_j, or n^-1 sum_j w^(-jk) P_j with

@@ -1272,6 +1272,38 @@ int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t
     return BBG_OK;
 }
 
+int bbg_g1_msm_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries)
+{
+    return msm_points_plan(n, window_bits, c, windows, chunk_terms, segment_entries);
+}
+
+int bbg_g1_msm_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int window_bits, void* d_out_affine)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return msm_points_run(ctx, d_points_affine, d_scalars, n, window_bits, d_out_affine, ctx->stream);
+}
+
+int bbg_g1_msm(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t* scalars, size_t n, int window_bits, uint64_t out_affine[8])
+{
+    CHECK_CTX(ctx);
+    if (!out_affine || (n && (!points_affine || !scalars))) { set_error("bbg_g1_msm: null argument"); return BBG_E_INVALID; }
+    if (int rc = msm_points_plan(n, window_bits, nullptr, nullptr, nullptr, nullptr)) return rc; // before the staging buffer is sized by n
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int rc = ctx->staging.ensure(64 + n * 96);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p; // result | points | scalars
+    if (n) {
+        BBG_HIP(hipMemcpyAsync(st + 64, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
+        BBG_HIP(hipMemcpyAsync(st + 64 + n * 64, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = msm_points_run(ctx, st + 64, st + 64 + n * 64, n, window_bits, st, ctx->stream);
+    if (rc) return rc;
+    BBG_HIP(hipMemcpyAsync(out_affine, st, 64, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    return BBG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ NTT
 int bbg_ntt_prepare(bbg_ctx* ctx, unsigned log2n)
 {

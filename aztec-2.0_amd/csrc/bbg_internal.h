@@ -203,13 +203,15 @@ struct bbg_ctx {
     void* cells_pinned = nullptr;
     size_t cells_pinned_bytes = 0;
     hipEvent_t cells_copied = nullptr;
+    // msm_points.hip: the working set of one bbg_g1_msm call (buckets, group sums, partial sums, the counting sort's arrays), at most 1 GiB
+    bbg::DevBuf msm_points_work;
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
 };
 
 // every context buffer that bbg_memory_report counts under `scratch`: a new buffer is one member above plus one entry here
 constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::ntt_scratch, &bbg_ctx::staging,  &bbg_ctx::poly_scratch, &bbg_ctx::gp_totals,  &bbg_ctx::quot_setup,
-    &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,   &bbg_ctx::cells_work,
+    &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,   &bbg_ctx::cells_work, &bbg_ctx::msm_points_work,
 };
 
 // bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle.
@@ -363,6 +365,11 @@ int var_base_mul(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size
 // the lanes (a multiple of 64, at most "batch_mul_lanes") a variable-base kernel with `work` items runs on, and their tables in the
 // context's buffer (1 KiB per lane, grown on demand)
 int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables);
+// msm_points.hip: *d_out = sum_i d_scalars[i] d_points[i] over plain arrays, 64 B canonical affine (aff_inf() for infinity,
+// n = 0 included); window_bits 0 = automatic, else 2 .. 16.  Every argument error is BBG_E_INVALID before anything is queued.  Queues only.
+int msm_points_run(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size_t n, int window_bits, void* d_out, hipStream_t stream);
+// what such a call runs with (any out pointer may be null); needs no device
+int msm_points_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries);
 // open_all.hip
 int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out);
 int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);

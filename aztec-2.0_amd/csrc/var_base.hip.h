@@ -154,6 +154,46 @@ __device__ __forceinline__ GlvHalves glv_split(const Fr& k)
     return r;
 }
 
+// The same split with the PLAIN magnitudes, for callers that recode the halves themselves (msm_points.hip): m1 = |k1| (k1 is never
+// negative), m2 = |k2|, four limbs each; returns k2 < 0.  A body of its own, so that glv_split and the kernels built on it compile as
+// they did; tests/tools/var_base_model.py split() is the model of both.
+__device__ __forceinline__ bool glv_split_mag(const Fr& k, uint32_t* m1, uint32_t* m2)
+{
+    using namespace glv;
+    uint32_t g1[5], g2[3], mb1[4], b2[2], a2[4];
+#pragma unroll
+    for (int i = 0; i < 5; i++) g1[i] = GlvP::G1[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) g2[i] = GlvP::G2[i];
+#pragma unroll
+    for (int i = 0; i < 4; i++) mb1[i] = GlvP::MB1[i], a2[i] = GlvP::A2[i];
+#pragma unroll
+    for (int i = 0; i < 2; i++) b2[i] = GlvP::B2[i];
+    uint32_t c1[3], c2[5];
+    mul_cols<8, 3, 8, 3>(c1, k.v, g2);
+    mul_cols<8, 5, 8, 5>(c2, k.v, g1);
+    uint32_t k1[5], k2[5], t[5];
+    mul_cols<4, 2, 0, 5>(k2, c2, b2); // k2 = c2 b2 - c1 (-b1)   (mod 2^160)
+    mul_cols<2, 4, 0, 5>(t, c1, mb1);
+    sub160(k2, t);
+#pragma unroll
+    for (int i = 0; i < 5; i++) k1[i] = k.v[i]; // k1 = k - c1 a1 - c2 a2  (mod 2^160), a1 = b2
+    mul_cols<2, 2, 0, 5>(t, c1, b2);
+    sub160(k1, t);
+    mul_cols<4, 4, 0, 5>(t, c2, a2);
+    sub160(k1, t);
+    const bool neg2 = (k2[4] >> 31) != 0;
+    if (neg2) { // |k2| = 0 - k2
+        uint32_t z[5] = { 0, 0, 0, 0, 0 };
+        sub160(z, k2);
+#pragma unroll
+        for (int i = 0; i < 5; i++) k2[i] = z[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) m1[i] = k1[i], m2[i] = k2[i];
+    return neg2;
+}
+
 // ---------------------------------------------------------------------------------------------- table and rounds
 constexpr int GLV_TABLE = 8;                                  // odd multiples P, 3P .. 15P
 constexpr size_t GLV_TABLE_BYTES = GLV_TABLE * sizeof(Xyzz);  // 1 KiB per lane

@@ -174,6 +174,40 @@ int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t
  * in place); an output that overlaps the points in any other way, or overlaps the scalars, is refused with BBG_E_INVALID. */
 int bbg_g1_batch_mul_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int one_scalar, void* d_out_affine);
 
+/* A multi-scalar multiplication over the CALLER'S points: out_affine = sum_(i<n) scalars[i] * points_affine[i], with no bbg_srs and no
+ * window tables (csrc/msm_points.hip; bbg_msm* needs a registered string and its precomputed tables).  points: 64-byte
+ * Montgomery affine, any representative in [0, 2p) per coordinate; the affine encoding of infinity is accepted as data and contributes
+ * nothing.  Points are NOT checked to be on the curve: for a point off it the result is unspecified (but nothing else is affected).
+ * scalars: Montgomery Fr, any representative in [0, 2r).  out: ONE canonical Montgomery affine point of 64 bytes; a result at infinity is
+ * written exactly as bbg_g1_fixed_base_mul writes it (bit 63 of x.data[3] set, every other bit zero).  n = 0 is legal and writes infinity.
+ * The output being canonical, the order of the additions does not show: the result is a function of the inputs alone.
+ *   window_bits   0 = automatic (a function of n alone, as measured on an MI355X: 4 up to 2^12 terms, 8 up to 2^15, 9 up to 2^17, 16
+ *                 above), or a width c in 2 .. 16; anything else is BBG_E_INVALID.  windows(c) = ceil(128 / c) signed c-bit digits per
+ *                 half scalar.  A forced width is taken as given and is not tuned for small n: from 14 bits (65536 buckets and
+ *                 more) a bucket's run is summed by one lane, below by one whole wave, whatever n is, so a wide forced width over a few
+ *                 hundred terms spends a wave and a search on every one-entry bucket.
+ *   n             at most 2^28; more is BBG_E_INVALID.
+ * Null pointers with n > 0 (and a null out always) are BBG_E_INVALID.  Each scalar is split against the cube root of unity into two
+ * halves below 2^127 and recoded into signed digits; the 2 n windows(c) non-zero digits are grouped by bucket with a counting sort, the
+ * buckets summed by mixed additions (a bucket longer than segment_entries is cut into segments summed by different lanes or waves, so
+ * no input makes one lane's chain longer), and reduced per window by running sums.  Terms are walked in chunks of chunk_terms.  Working
+ * memory: at most 1 GiB, 128 (2 B + 2 windows G + windows + E / segment_entries) + 16 (B + 1) + 8 E bytes (B = windows 2^(c-1) buckets,
+ * G = 2^(c-1) / min(2^(c-1), 32) groups per window, E = 2 windows min(n, chunk_terms) entries) plus less than 2 KiB of alignment, counted
+ * under `scratch` in bbg_memory_report and released by bbg_memory_trim.  Timed under "msm_points_sort", "msm_points_accumulate",
+ * "msm_points_reduce", "msm_points_combine" (bbg_profile_get). */
+int bbg_g1_msm(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t* scalars, size_t n, int window_bits, uint64_t out_affine[8]);
+/* Device-resident: device pointers, asynchronous on the context stream, no host synchronisation once the working memory has its size.
+ * That size depends on BOTH window_bits and n (the formula above): the buffer only grows, and a call that needs more than any call
+ * before it -- a larger n, or another width, forced or automatic -- waits for the device once while the buffer is replaced; calls that
+ * fit what is there only queue.  The inputs are left untouched.  An output that overlaps the points or the scalars is BBG_E_INVALID; every argument error is decided
+ * before anything is queued. */
+int bbg_g1_msm_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int window_bits, void* d_out_affine);
+/* What a call with these arguments would run with; a pure host function that needs no device and no context.  *c: the width used,
+ * *windows: digits per half scalar, *chunk_terms: terms per chunk (a function of the width alone: 2^20, less where 1 GiB asks for it),
+ * *segment_entries: the longest run of one bucket's entries that one lane (256, from 65536 buckets) or one wave (1024) sums.  Any out
+ * pointer may be NULL.  BBG_E_INVALID for a window_bits or an n that the call would refuse. */
+int bbg_g1_msm_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries);
+
 /* The NTT over G1 on plain arrays of points (no counterpart in the reference beyond the recursion inside transform_srs): with n = 2^log2n,
  * 1 <= log2n <= 28, and w_n = fr::get_root_of_unity(log2n), natural order in and out,
  *     out[k] = sum_j w_n^(j k) P_j            (inverse == 0)
@@ -575,7 +609,7 @@ typedef struct bbg_memory_info {
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
     size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
                               variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover,
-                              the working set of bbg_cells_verify_reduce */
+                              the working set of bbg_cells_verify_reduce, the working memory of bbg_g1_msm */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
@@ -629,7 +663,8 @@ int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
  * "msm_accumulate", "msm_reduce", "ntt_pass", "quotient_widget", "ecntt_stages", "ecntt_normalize", "fixed_base_table", "fixed_base_mul", "var_base_mul",
  * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum",
  * "cells_gather", "cells_z", "cells_scatter", "cells_divide", "cells_canon", "cells_verify_powers", "cells_verify_fold", "cells_verify_mul",
- * "cells_verify_segsum", "cells_verify_phi", "cells_verify_finish".  enable(…, 1) clears previous samples. */
+ * "cells_verify_segsum", "cells_verify_phi", "cells_verify_finish", "msm_points_sort", "msm_points_accumulate", "msm_points_reduce",
+ * "msm_points_combine".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
