@@ -91,6 +91,13 @@ def load_library():
         "bbg_g1_msm": (cint, [vp, vp, vp, sz, cint, vp]),
         "bbg_g1_msm_device": (cint, [vp, vp, vp, sz, cint, vp]),
         "bbg_g1_msm_plan": (cint, [sz, cint, ctypes.POINTER(cint), ctypes.POINTER(cint), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "bbg_g2_mul": (cint, [vp, vp, vp, sz, vp]),
+        "bbg_g2_lines_prepare": (cint, [vp, vp, sz, ctypes.POINTER(vp)]),
+        "bbg_g2_lines_pairs": (cint, [vp, ctypes.POINTER(sz)]),
+        "bbg_g2_lines_read": (cint, [vp, sz, vp]),
+        "bbg_g2_lines_free": (None, [vp]),
+        "bbg_pairing_product_device": (cint, [vp, vp, vp, sz, vp, vp]),
+        "bbg_pairing_product": (cint, [vp, vp, vp, sz, vp, vp]),
         "bbg_g1_ntt": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_g1_ntt_device": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_open_all_prepare": (cint, [vp, vp, ctypes.c_uint, ctypes.POINTER(vp)]),
@@ -201,6 +208,8 @@ EXPORTED_SYMBOLS = [
     "bbg_cells_values_device", "bbg_cells_values", "bbg_cells_recover_device", "bbg_cells_recover",
     "bbg_cells_verify_reduce_device", "bbg_cells_verify_reduce",
     "bbg_g1_msm", "bbg_g1_msm_device", "bbg_g1_msm_plan",
+    "bbg_g2_mul", "bbg_g2_lines_prepare", "bbg_g2_lines_pairs", "bbg_g2_lines_read", "bbg_g2_lines_free",
+    "bbg_pairing_product_device", "bbg_pairing_product",
 ]
 
 
@@ -314,6 +323,30 @@ class OpenAll:
     def free(self):
         if self.handle:
             self._owner.lib.bbg_open_all_free(self.handle)
+            self.handle = None
+
+
+class G2Lines:
+    """A prepared bbg_g2_lines handle: the line coefficients of `pairs` G2 points, the fixed side of bbg_pairing_product."""
+
+    def __init__(self, owner, handle):
+        self._owner, self.handle = owner, handle
+
+    @property
+    def pairs(self):
+        c = ctypes.c_size_t()
+        self._owner._ck(self._owner.lib.bbg_g2_lines_pairs(self.handle, ctypes.byref(c)))
+        return int(c.value)
+
+    def read(self, which):
+        """The 2088 words (16 704 bytes) of pairing::miller_lines of point `which` (bbg_g2_lines_read)."""
+        out = np.zeros(2088, dtype=np.uint64)
+        self._owner._ck(self._owner.lib.bbg_g2_lines_read(self.handle, which, out.ctypes.data))
+        return out
+
+    def free(self):
+        if self.handle:
+            self._owner.lib.bbg_g2_lines_free(self.handle)
             self.handle = None
 
 
@@ -507,6 +540,42 @@ class Bbg:
         if lib.bbg_g1_msm_plan(n, int(window_bits), ctypes.byref(c), ctypes.byref(windows), ctypes.byref(chunk), ctypes.byref(seg)) != 0:
             raise BbgError(lib.bbg_last_error().decode())
         return c.value, windows.value, chunk.value, seg.value
+
+    # ---- G2 and pairing product checks (csrc/pairing.hip)
+    def g2_mul(self, scalars, base=None):
+        """scalars[i] * base on the twist as (n, 16) canonical affine points x | y; base = one point (16 limbs), None = the generator of G2;
+        infinity in the affine encoding applied to x.c0 (bbg_g2_mul)."""
+        sc = _u64(scalars, 4)
+        b = None if base is None else np.ascontiguousarray(base, dtype=np.uint64).reshape(16)
+        out = np.zeros((sc.shape[0], 16), dtype=np.uint64)
+        self._ck(self.lib.bbg_g2_mul(self.ctx, None if b is None else b.ctypes.data, sc.ctypes.data, sc.shape[0], out.ctypes.data))
+        return out
+
+    def g2_lines_prepare(self, g2_points):
+        """A G2Lines for (pairs, 16) finite points of the order-r subgroup of the twist, 1 <= pairs <= 8 (bbg_g2_lines_prepare)."""
+        q = _u64(g2_points, 16)
+        h = ctypes.c_void_p()
+        self._ck(self.lib.bbg_g2_lines_prepare(self.ctx, q.ctypes.data, q.shape[0], ctypes.byref(h)))
+        return G2Lines(self, h)
+
+    def pairing_product(self, lines, g1_points, want_values=True):
+        """(values, status) of count products over (count * pairs, 8) affine G1 points, product i pairing point i pairs + j with point j of
+        `lines`: values (count, 48) canonical fq12 words (None without want_values), status (count,) uint32 with 1 = the product is one,
+        0 = it is not.  A G1 point off the curve raises BbgError (bbg_pairing_product)."""
+        p = _u64(g1_points, 8)
+        count, rest = divmod(p.shape[0], lines.pairs)
+        if rest:
+            raise ValueError(f"expected a multiple of {lines.pairs} points, got {p.shape[0]}")
+        values = np.zeros((count, 48), dtype=np.uint64) if want_values else None
+        status = np.zeros(count, dtype=np.uint32)
+        self._ck(self.lib.bbg_pairing_product(self.ctx, lines.handle, p.ctypes.data, count, None if values is None else values.ctypes.data, status.ctypes.data))
+        return values, status
+
+    def pairing_product_device(self, lines, d_g1_points, count, d_out_fq12=None, d_status=None):
+        """Device pointers (count x pairs x 64 B in; count x 384 B and count x 4 B out, either may be None); asynchronous on the context
+        stream (bbg_pairing_product_device)."""
+        self._ck(self.lib.bbg_pairing_product_device(self.ctx, lines.handle, ctypes.c_void_p(d_g1_points), count,
+                                                     ctypes.c_void_p(d_out_fq12) if d_out_fq12 else None, ctypes.c_void_p(d_status) if d_status else None))
 
     def g1_ntt(self, points, inverse=False):
         """The NTT over G1 of (n, 8) affine points, n a power of two >= 2: out[k] = sum_j w^(jk) P_j, or n^-1 sum_j w^(-jk) P_j with

@@ -1304,6 +1304,65 @@ int bbg_g1_msm(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t* scal
     return BBG_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ G2 and the pairing (pairing.hip)
+int bbg_g2_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return g2_mul_host(ctx, base_affine, scalars, n, out_affine, ctx->stream);
+}
+
+int bbg_g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, bbg_g2_lines** out)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return g2_lines_prepare(ctx, g2_affine, pairs, out, ctx->stream);
+}
+
+int bbg_g2_lines_pairs(const bbg_g2_lines* lines, size_t* pairs)
+{
+    if (!lines || !pairs) { set_error("bbg_g2_lines_pairs: null argument"); return BBG_E_INVALID; }
+    *pairs = lines->pairs;
+    return BBG_OK;
+}
+
+int bbg_g2_lines_read(const bbg_g2_lines* lines, size_t which, uint64_t* out) { return g2_lines_read(lines, which, out); }
+
+void bbg_g2_lines_free(bbg_g2_lines* lines) { g2_lines_release(lines); }
+
+int bbg_pairing_product_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d_g1_affine, size_t count, void* d_out_fq12, void* d_status)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return pairing_product_run(ctx, lines, d_g1_affine, count, d_out_fq12, d_status, ctx->stream);
+}
+
+int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status)
+{
+    CHECK_CTX(ctx);
+    if (int rc = pairing_product_check("bbg_pairing_product", ctx, lines, g1_affine, count, out_fq12, status)) return rc; // before the staging buffer is sized by count
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t in_bytes = count * lines->pairs * 64;
+    int rc = ctx->staging.ensure(count * 388 + in_bytes);
+    if (rc) return rc;
+    char* st = (char*)ctx->staging.p; // values | points | status
+    char *d_in = st + count * 384, *d_flags = d_in + in_bytes;
+    BBG_HIP(hipMemcpyAsync(d_in, g1_affine, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = pairing_product_run(ctx, lines, d_in, count, st, d_flags, ctx->stream);
+    if (rc) return rc;
+    std::vector<uint32_t> flags(count);
+    BBG_HIP(hipMemcpyAsync(flags.data(), d_flags, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_fq12) BBG_HIP(hipMemcpyAsync(out_fq12, st, count * 384, hipMemcpyDeviceToHost, ctx->stream));
+    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    if (status) memcpy(status, flags.data(), count * 4);
+    const size_t off_curve = (size_t)std::count(flags.begin(), flags.end(), 2u);
+    if (off_curve) {
+        set_error("bbg_pairing_product: " + std::to_string(off_curve) + " of the products have a G1 point that is not on the curve");
+        return BBG_E_INVALID;
+    }
+    return BBG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ NTT
 int bbg_ntt_prepare(bbg_ctx* ctx, unsigned log2n)
 {

@@ -205,6 +205,8 @@ struct bbg_ctx {
     hipEvent_t cells_copied = nullptr;
     // msm_points.hip: the working set of one bbg_g1_msm call (buckets, group sums, partial sums, the counting sort's arrays), at most 1 GiB
     bbg::DevBuf msm_points_work;
+    // pairing.hip: the working set of one bbg_pairing_product call: six lane-interleaved Fq12 slots and a flag word for at most 2^16 products
+    bbg::DevBuf pairing_work;
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
 };
 
@@ -212,6 +214,7 @@ struct bbg_ctx {
 constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::ntt_scratch, &bbg_ctx::staging,  &bbg_ctx::poly_scratch, &bbg_ctx::gp_totals,  &bbg_ctx::quot_setup,
     &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,   &bbg_ctx::cells_work, &bbg_ctx::msm_points_work,
+    &bbg_ctx::pairing_work,
 };
 
 // bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle.
@@ -230,6 +233,14 @@ struct bbg_open_all {
     void* batch_ws = nullptr;
     size_t batch_cap = 0;
     bool batch_lds_attr = false; // the LDS transform's dynamic-LDS limit is raised on this handle's device (hipFuncSetAttribute is per device)
+};
+
+// bbg_g2_lines_prepare (pairing.hip): the line coefficients of `pairs` G2 points, pairs x 16 704 B in the reference's pairing::miller_lines
+// layout, owned by the handle
+struct bbg_g2_lines {
+    int device = 0;
+    size_t pairs = 0;
+    void* d_lines = nullptr;
 };
 
 struct bbg_srs {
@@ -370,6 +381,17 @@ int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables);
 int msm_points_run(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size_t n, int window_bits, void* d_out, hipStream_t stream);
 // what such a call runs with (any out pointer may be null); needs no device
 int msm_points_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries);
+// pairing.hip.  out_affine[i] = [scalars[i]] base on the twist: HOST arrays, base_affine NULL = the generator of G2; waits for `stream`.
+int g2_mul_host(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine, hipStream_t stream);
+// the lines of `pairs` finite points of the order-r subgroup of the twist (HOST, 128 B each); anything else is BBG_E_INVALID.  Waits for `stream`.
+int g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, struct bbg_g2_lines** out, hipStream_t stream);
+int g2_lines_read(const struct bbg_g2_lines* h, size_t which, uint64_t* out);
+void g2_lines_release(struct bbg_g2_lines* h);
+// the argument checks of bbg_pairing_product[_device] that look at no device memory: BBG_E_INVALID with the error text set
+int pairing_product_check(const char* who, const bbg_ctx* ctx, const struct bbg_g2_lines* h, const void* points, size_t count, const void* out, const void* status);
+// d_out_fq12[i] (may be null) = prod_j e(d_g1[i pairs + j], Q_j), canonical; d_status[i] (may be null) = 1: the product is one, 0: it is not, 2: a
+// finite point of product i is off the curve.  Queues only once ctx->pairing_work has its size.
+int pairing_product_run(bbg_ctx* ctx, const struct bbg_g2_lines* h, const void* d_g1, size_t count, void* d_out_fq12, void* d_status, hipStream_t stream);
 // open_all.hip
 int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out);
 int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);

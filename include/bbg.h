@@ -208,6 +208,60 @@ int bbg_g1_msm_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_s
  * pointer may be NULL.  BBG_E_INVALID for a window_bits or an n that the call would refuse. */
 int bbg_g1_msm_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries);
 
+/* ---- G2 and batched pairing product checks over precomputed lines (csrc/pairing.hip, csrc/fq_tower.hip.h): for `count`
+ *      independent products over the SAME `pairs` G2 points Q_j,
+ *          e_i = prod_(j < pairs) e(P_ij, Q_j),        status_i = (e_i == 1),
+ *      what pairing::reduced_ate_pairing_batch_precomputed (ecc/curves/bn254/pairing_impl.hpp:269-282) computes once per product.  In KZG
+ *      verification the G2 points are fixed ([1]_2 and [x]_2 or [x^l]_2), so their line coefficients are computed once per handle and
+ *      every product evaluates the same lines at its own G1 points: e(L, [x^l]_2) e(-R, [1]_2) = 1 is the check bbg_cells_verify_reduce
+ *      leaves.  Layouts are the reference's, Montgomery form: fq2 = c0 | c1 (64 B), fq6 = c0 | c1 | c2, fq12 = c0 | c1 (384 B),
+ *      g2::affine_element = x | y (128 B), pairing::miller_lines = 87 x (o | vw | vv) (16 704 B).  Fq inputs: any representative in
+ *      [0, 2p) per Fq limb group; every output is canonical. ---- */
+#define BBG_PAIRING_MAX_PAIRS 8
+typedef struct bbg_g2_lines bbg_g2_lines;
+/* out_affine[i] = [scalars[i]] B on the twist y^2 = x^3 + 3 / (9 + u), i < n: double-and-add, one lane per scalar (plumbing, not a hot
+ * path: it makes [x^l]_2 and runs the subgroup test of bbg_g2_lines_prepare).  base_affine: one 128-byte point on the HOST, NULL =
+ * g2::one, the generator; the affine encoding of infinity (below) is accepted and gives infinity.  A finite base that is not on the twist
+ * is BBG_E_INVALID (n = 0 included) with out_affine untouched; it need not be in the order-r subgroup.  scalars: Montgomery Fr, any
+ * representative in [0, 2r).  out: canonical 128-byte points; a result at infinity (scalar = 0 mod the point's order, or an infinite base)
+ * is written in the reference's affine infinity encoding applied to x.c0: bit 63 of the top limb of x.c0 (word 3 of the 16) set, every
+ * other bit of the 128 bytes zero.  All arrays are HOST arrays; the call is synchronous.  n is at most 2^16: more is BBG_E_INVALID.
+ * n = 0 is legal; null scalars or out with n > 0 are BBG_E_INVALID. */
+int bbg_g2_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine);
+/* The 87 line coefficients (precompute_miller_lines, pairing_impl.hpp:23-123) of `pairs` (1 .. BBG_PAIRING_MAX_PAIRS) G2 points, 128 bytes
+ * each on the HOST, as a handle.  Every point must be finite, on the twist, and in the subgroup of order r: the subgroup test is [r] Q =
+ * infinity, once per point (G2 has a cofactor, and a pairing check against a point outside the subgroup proves nothing).  A violation,
+ * like a null argument or a bad `pairs`, is BBG_E_INVALID and leaves *out untouched.  The call synchronises.  The handle owns its
+ * pairs x 16 704 bytes of device memory and keeps nothing of the caller's; it belongs to the context's device and may be used by any
+ * context on that device.  Timed under "g2_lines" (bbg_profile_get). */
+int bbg_g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, bbg_g2_lines** out);
+int bbg_g2_lines_pairs(const bbg_g2_lines* lines, size_t* pairs);
+/* out (HOST, 16 704 bytes) = the lines of point `which` < pairs, bit for bit the canonical pairing::miller_lines that
+ * precompute_miller_lines makes of it; synchronous. */
+int bbg_g2_lines_read(const bbg_g2_lines* lines, size_t which, uint64_t* out);
+void bbg_g2_lines_free(bbg_g2_lines* lines);
+/* d_g1_affine: count x pairs Montgomery affine G1 points of 64 bytes, product i pairing point (i, j) at index i pairs + j with the
+ * handle's point j.  The affine encoding of infinity is accepted as data: such a pair contributes the factor one and its lines are
+ * skipped (L and R of bbg_cells_verify_reduce are both infinite when every polynomial has degree below l); a product whose pairs are all
+ * infinite is one.  d_out_fq12 (may be NULL): count x 384 bytes, for finite inputs bit for bit the canonical form of
+ * reduced_ate_pairing_batch_precomputed(P_i, lines, pairs).  d_status (may be NULL): count uint32 words,
+ *     1   the product is one in Fq12
+ *     0   it is not
+ *     2   some finite G1 point of this product is not on y^2 = x^3 + 3; the Fq12 written for that product is unspecified and nothing
+ *         else is affected.
+ * BBG_E_INVALID with nothing queued: a null context, handle or d_g1_affine; both outputs null; count = 0 or above 2^24; a handle made on
+ * another device; an output overlapping the input or the other output.
+ * Queued on the context stream with no host synchronisation once the working memory has its size: 2308 bytes (six Fq12 values and one
+ * flag word) per product for min(count, 2^16) products rounded up to a multiple of 64 -- at most 145 MiB; longer batches are walked in
+ * chunks of 2^16.  The buffer only grows: a call that needs more than any call before waits for the device once.  It is counted under
+ * `scratch` in bbg_memory_report and released by bbg_memory_trim.  Timed under "pairing_miller" (the Miller loop: 64 Fq12 squarings and
+ * 87 sparse products per pair, one lane per product) and "pairing_final" (the final exponentiation) (bbg_profile_get). */
+int bbg_pairing_product_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d_g1_affine, size_t count, void* d_out_fq12, void* d_status);
+/* The same on HOST arrays (out_fq12: count x 48 words, status: count words; either may be NULL, not both); synchronous.  A status 2
+ * anywhere returns BBG_E_INVALID after both outputs have been written, so the caller can see which product it was; every other error
+ * leaves them untouched. */
+int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status);
+
 /* The NTT over G1 on plain arrays of points (no counterpart in the reference beyond the recursion inside transform_srs): with n = 2^log2n,
  * 1 <= log2n <= 28, and w_n = fr::get_root_of_unity(log2n), natural order in and out,
  *     out[k] = sum_j w_n^(j k) P_j            (inverse == 0)
@@ -251,7 +305,7 @@ int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_
  *   The VALUES of cell m are f(w_n^(m + r t)), t < l: bbg_ntt(BBG_FFT) of the n coefficients, read at index m with stride r.
  * bbg_cells_values writes them cell by cell, and bbg_cells_recover gives the coefficients back from any K of the r cells (below).
  * Verification: bbg_cells_verify_reduce (below) reduces any batch of cell proofs to two G1 points L, R with e(L, [x^l]_2) = e(R, [1]_2)
- * iff every proof is valid.  The caller still owes that one two-pair pairing against [x^l]_2, a G2 point this library does not make, and
+ * iff every proof is valid.  The caller still owes that one two-pair pairing against [x^l]_2 (bbg_g2_mul makes the point, bbg_pairing_product the check), and
  * the choice of the challenge rho. */
 int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
 /* The number of proofs a call writes: n >> log2cell (n for a handle of bbg_open_all_prepare). */
@@ -309,7 +363,7 @@ int bbg_cells_recover_device(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, c
 int bbg_cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const uint64_t* values, unsigned log2n, unsigned log2cell, size_t count,
                       uint64_t* out_coeffs);
 /* ---- a batch of cell proofs reduced to ONE pairing check (csrc/cells_verify.hip): everything a verifier of cell proofs computes in G1 and
- *      Fr, up to the pairing, which stays the caller's.  A batch has ncom commitments C_c and K cells; cell k < K carries a commitment index
+ *      Fr, up to the pairing, which is bbg_pairing_product's (above).  A batch has ncom commitments C_c and K cells; cell k < K carries a commitment index
  *      commitment_ids[k] < ncom, a cell index cell_ids[k] < r, the l values of that cell at values[k l .. k l + l) in bbg_cells_values'
  *      order within the cell, and a proof pi_k (what bbg_open_all_device writes for that cell).  With I_k the interpolant of degree < l
  *      through the values, s_b the first l points of `srs` and rho the caller's challenge, the call writes
@@ -609,7 +663,7 @@ typedef struct bbg_memory_info {
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
     size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
                               variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover,
-                              the working set of bbg_cells_verify_reduce, the working memory of bbg_g1_msm */
+                              the working set of bbg_cells_verify_reduce, the working memory of bbg_g1_msm and of bbg_pairing_product */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
@@ -664,7 +718,7 @@ int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
  * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum",
  * "cells_gather", "cells_z", "cells_scatter", "cells_divide", "cells_canon", "cells_verify_powers", "cells_verify_fold", "cells_verify_mul",
  * "cells_verify_segsum", "cells_verify_phi", "cells_verify_finish", "msm_points_sort", "msm_points_accumulate", "msm_points_reduce",
- * "msm_points_combine".  enable(…, 1) clears previous samples. */
+ * "msm_points_combine", "g2_lines", "pairing_miller", "pairing_final".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
