@@ -1,6 +1,12 @@
 // C ABI of libbbg.so (declared in include/bbg.h).  Host-side plumbing only: contexts, device buffers, the SRS
 // registry and the Ignition-transcript reader.  All arithmetic runs in the HIP kernels of ntt.hip / msm.hip.
+//
+// Most calls come as a *_device form on device pointers (the context lock, then the module) and a host-array twin, which reads: argument
+// checks, regions, upload, run, download.  Its regions are those of one Staged call (below): a StageLayout (stage_layout.h: offsets aligned
+// to 256 B, overflow reported) over ctx->staging, sized once; no entry point computes an offset into the staging buffer by hand.  The
+// checks several entry points word alike (log2n in a range, an SRS too short or on another device, a zero scalar) are bbg_internal.h's check_*.
 #include "bbg_internal.h"
+#include "stage_layout.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -56,7 +62,55 @@ struct ScopedMem {
         if (p) (void)(host ? hipHostFree(p) : hipFree(p));
     }
 };
+
+// One staged call of a host-array entry point: a StageLayout bound to the context's staging buffer and stream.  The entry point asks for
+// its regions in order (each as large as the device call behind it may touch, slack included), ensure() sizes the buffer once -- a layout
+// that does not fit size_t is "<who>: size out of range" -- and st[region] is a pointer from then on; up() and down() queue the copies,
+// wait() ends the call.  Every step returns BBG_OK or the code of the HIP error with the text set.  The caller holds ctx->mu throughout.
+class Staged {
+  public:
+    struct Region { size_t off; };
+    Staged(bbg_ctx* c, const char* who_) : ctx(c), who(who_) {}
+    Region region(size_t bytes) { return { lay.add(bytes) }; }
+    Region region(size_t count, size_t each) { return { lay.add(count, each) }; }
+    int ensure()
+    {
+        if (!lay.ok()) { set_error(std::string(who) + ": size out of range"); return BBG_E_INVALID; }
+        return ctx->staging.ensure(lay.total());
+    }
+    char* operator[](Region r) const { return (char*)ctx->staging.p + r.off; }
+    int up(Region r, const void* host, size_t bytes) { BBG_HIP(hipMemcpyAsync((*this)[r], host, bytes, hipMemcpyHostToDevice, ctx->stream)); return BBG_OK; }
+    int down(void* host, Region r, size_t bytes) { BBG_HIP(hipMemcpyAsync(host, (*this)[r], bytes, hipMemcpyDeviceToHost, ctx->stream)); return BBG_OK; }
+    int wait() { BBG_HIP(hipStreamSynchronize(ctx->stream)); return BBG_OK; }
+
+  private:
+    bbg_ctx* ctx;
+    const char* who;
+    StageLayout lay;
+};
+// `step` is a Staged step or a module's run: leave the entry point with its code unless it is BBG_OK
+#define BBG_TRY(step) do { if (int _rc = (step)) return _rc; } while (0)
 } // namespace
+
+// the argument checks of bbg_internal.h
+static const uint64_t R_MOD[4] = { 0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL }; // the modulus of Fr
+static int invalid(const char* who, const std::string& sentence) { set_error(std::string(who) + ": " + sentence); return BBG_E_INVALID; }
+int check_log2n(const char* who, unsigned log2n, unsigned lo, unsigned hi)
+{
+    return log2n < lo || log2n > hi ? invalid(who, "log2n must be " + std::to_string(lo) + " .. " + std::to_string(hi)) : BBG_OK;
+}
+int check_srs_holds(const char* who, const Srs& srs, unsigned log2, const char* name)
+{
+    return ((size_t)1 << log2) > srs.n ? invalid(who, std::string("the SRS holds fewer than 2^") + name + " points") : BBG_OK;
+}
+int check_srs_device(const char* who, const Srs& srs, const bbg_ctx* ctx, const char* hint)
+{
+    return srs.device != ctx->device ? invalid(who, std::string("the SRS lives on another device than the context") + hint) : BBG_OK;
+}
+int check_fr_nonzero(const char* who, const uint64_t v[4], const char* what) // the two representatives of 0 in [0, 2r)
+{
+    return (v[0] | v[1] | v[2] | v[3]) == 0 || memcmp(v, R_MOD, 32) == 0 ? invalid(who, what) : BBG_OK;
+}
 int srs_build_tables(const void* d_points, size_t n, void* d_table, int c, hipStream_t st);
 int msm_pick_window(const bbg_ctx* ctx, size_t n);
 void prover_report(const bbg_ctx* ctx, size_t* bytes, unsigned* count); // prover.hip: live bbg_prover handles of a context
@@ -109,6 +163,32 @@ static int make_srs(bbg_ctx* ctx, const void* d_plain_points, size_t n, bbg_srs*
     }
     *out = s;
     return BBG_OK;
+}
+
+// What the SRS constructors share: n plain points (64 B each) in a buffer of the call's own, filled by fill(d_plain) on the context's stream
+// and then registered.  Not the staging buffer: make_srs reads the points after the fill, behind whatever the fill itself staged.
+template <class Fill> static int srs_from_filled(bbg_ctx* ctx, size_t n, bbg_srs** out, Fill fill)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ScopedMem d_plain;
+    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
+    int rc = fill(d_plain.p);
+    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, n, out); // window tables + the synchronisation
+    return rc;
+}
+// The same for a string of powers: d_pow[i] = s^i, i < n (32 n bytes of working memory beside the points, freed before return), then
+// mul(d_pow, d_plain) turns them into the points.  `what` names the working set in the text of an allocation failure.
+template <class Mul> static int srs_from_powers(bbg_ctx* ctx, const char* what, const uint64_t s[4], size_t n, bbg_srs** out, Mul mul)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ScopedMem d_plain, d_pow;
+    hipError_t e = hipMalloc(&d_plain.p, n * 64);
+    if (e == hipSuccess) e = hipMalloc(&d_pow.p, n * 32);
+    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
+    int rc = fixed_base_powers(s, n, d_pow.p, ctx->stream);
+    if (rc == BBG_OK) rc = mul(d_pow.p, d_plain.p);
+    if (rc) return rc;
+    return make_srs(ctx, d_plain.p, n, out); // window tables + the synchronisation
 }
 
 // ------------------------------------------------------------------------------------------------ options (bbg_set_option)
@@ -489,16 +569,11 @@ int bbg_srs_register(bbg_ctx* ctx, const uint64_t* points, size_t n, size_t stri
         set_error("bbg_srs_register: stride_bytes must be 64 (plain points) or 128 (interleaved endomorphism table)");
         return BBG_E_INVALID;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ScopedMem d_plain;
-    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
-    hipError_t e;
-    if (stride_bytes == 64)
-        e = hipMemcpyAsync(d_plain.p, points, n * 64, hipMemcpyHostToDevice, ctx->stream);
-    else
-        e = hipMemcpy2DAsync(d_plain.p, 64, points, 128, 64, n, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(e, "SRS upload", __FILE__, __LINE__);
-    return make_srs(ctx, d_plain.p, n, out);
+    return srs_from_filled(ctx, n, out, [&](void* d_plain) {
+        const hipError_t e = stride_bytes == 64 ? hipMemcpyAsync(d_plain, points, n * 64, hipMemcpyHostToDevice, ctx->stream)
+                                                : hipMemcpy2DAsync(d_plain, 64, points, 128, 64, n, hipMemcpyHostToDevice, ctx->stream);
+        return e == hipSuccess ? BBG_OK : hip_fail(e, "SRS upload", __FILE__, __LINE__);
+    });
 }
 
 int bbg_srs_register_device(bbg_ctx* ctx, const void* d_points, size_t n, bbg_srs** out)
@@ -514,73 +589,40 @@ int bbg_srs_synth_linear(bbg_ctx* ctx, uint64_t a, uint64_t s, size_t n, bbg_srs
     CHECK_CTX(ctx);
     if (!out) { set_error("bbg_srs_synth_linear: null out"); return BBG_E_INVALID; }
     if (s == 0 || a == 0) { set_error("bbg_srs_synth_linear: a and s must be non-zero"); return BBG_E_INVALID; }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ScopedMem d_plain;
-    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
-    int rc = srs_synth_linear(ctx, a, s, n, d_plain.p, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, n, out);
-    return rc;
+    return srs_from_filled(ctx, n, out, [&](void* d_plain) { return srs_synth_linear(ctx, a, s, n, d_plain, ctx->stream); });
 }
 
 int bbg_srs_synth_hashed(bbg_ctx* ctx, uint64_t seed, size_t n, bbg_srs** out)
 {
     CHECK_CTX(ctx);
     if (!out) { set_error("bbg_srs_synth_hashed: null out"); return BBG_E_INVALID; }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ScopedMem d_plain;
-    BBG_HIP(hipMalloc(&d_plain.p, n ? n * 64 : 64));
-    int rc = srs_synth_hashed(ctx, seed, n, d_plain.p, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, n, out);
-    return rc;
+    return srs_from_filled(ctx, n, out, [&](void* d_plain) { return srs_synth_hashed(ctx, seed, n, d_plain, ctx->stream); });
 }
 
-// Structured string P_i = [x^i] G: the powers x^i on the device (32 n bytes of working memory, freed before return), then the fixed-base
-// multiplication by the generator's table straight into the plain-point buffer (fixed_base.hip).
+// Structured string P_i = [x^i] G: the powers x^i on the device, then the fixed-base multiplication by the generator's table straight
+// into the plain-point buffer (fixed_base.hip).
 int bbg_srs_synth_powers(bbg_ctx* ctx, const uint64_t x[4], size_t n, bbg_srs** out)
 {
     CHECK_CTX(ctx);
     if (!out || !x) { set_error("bbg_srs_synth_powers: null argument"); return BBG_E_INVALID; }
     if (n == 0) { set_error("bbg_srs_synth_powers: n must be at least 1"); return BBG_E_INVALID; }
-    static const uint64_t R_MOD[4] = { 0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL };
-    if ((x[0] | x[1] | x[2] | x[3]) == 0 || memcmp(x, R_MOD, 32) == 0) { // the two representatives of 0 in [0, 2r)
-        set_error("bbg_srs_synth_powers: x = 0 (P_1 would be the point at infinity)");
-        return BBG_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ScopedMem d_plain, d_pow;
-    hipError_t e = hipMalloc(&d_plain.p, n * 64);
-    if (e == hipSuccess) e = hipMalloc(&d_pow.p, n * 32);
-    if (e != hipSuccess) return hip_fail(e, "bbg_srs_synth_powers: working set", __FILE__, __LINE__);
-    int rc = fixed_base_powers(x, n, d_pow.p, ctx->stream);
-    if (rc == BBG_OK) rc = fixed_base_mul(ctx, nullptr, d_pow.p, n, d_plain.p, ctx->stream);
-    if (rc) return rc;
-    return make_srs(ctx, d_plain.p, n, out); // window tables + the synchronisation
+    if (int rc = check_fr_nonzero("bbg_srs_synth_powers", x, "x = 0 (P_1 would be the point at infinity)")) return rc;
+    return srs_from_powers(ctx, "bbg_srs_synth_powers: working set", x, n, out,
+                           [&](const void* d_pow, void* d_plain) { return fixed_base_mul(ctx, nullptr, d_pow, n, d_plain, ctx->stream); });
 }
 
 // The update step of a powers-of-x string, P_i' = [y^i] P_i: the powers y^i on the device (k_fb_powers), the variable-base batch
-// multiplication (var_base.hip) from the SRS's plain points into a fresh buffer, then the registration.  32 n bytes of working memory
-// beside the result and the lanes' tables.
+// multiplication (var_base.hip) from the SRS's plain points into a fresh buffer, then the registration.  The lanes' tables beside it.
 int bbg_srs_scale_powers(bbg_ctx* ctx, bbg_srs* srs, const uint64_t y[4], bbg_srs** out)
 {
     CHECK_CTX(ctx);
     if (!srs || !y || !out) { set_error("bbg_srs_scale_powers: null argument"); return BBG_E_INVALID; }
-    if (srs->s.device != ctx->device) { set_error("bbg_srs_scale_powers: the SRS lives on another device than the context"); return BBG_E_INVALID; }
-    static const uint64_t R_MOD[4] = { 0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL };
-    if ((y[0] | y[1] | y[2] | y[3]) == 0 || memcmp(y, R_MOD, 32) == 0) { // the two representatives of 0 in [0, 2r)
-        set_error("bbg_srs_scale_powers: y = 0 (P_1 would become the point at infinity)");
-        return BBG_E_INVALID;
-    }
+    if (int rc = check_srs_device("bbg_srs_scale_powers", srs->s, ctx)) return rc;
+    if (int rc = check_fr_nonzero("bbg_srs_scale_powers", y, "y = 0 (P_1 would become the point at infinity)")) return rc;
     const size_t n = srs->s.n;
     if (n == 0) { set_error("bbg_srs_scale_powers: the SRS is empty"); return BBG_E_INVALID; }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ScopedMem d_plain, d_pow;
-    hipError_t e = hipMalloc(&d_plain.p, n * 64);
-    if (e == hipSuccess) e = hipMalloc(&d_pow.p, n * 32);
-    if (e != hipSuccess) return hip_fail(e, "bbg_srs_scale_powers: working set", __FILE__, __LINE__);
-    int rc = fixed_base_powers(y, n, d_pow.p, ctx->stream);
-    if (rc == BBG_OK) rc = var_base_mul(ctx, srs->s.points, d_pow.p, n, 0, d_plain.p, ctx->stream);
-    if (rc) return rc;
-    return make_srs(ctx, d_plain.p, n, out); // window tables + the synchronisation
+    return srs_from_powers(ctx, "bbg_srs_scale_powers: working set", y, n, out,
+                           [&](const void* d_pow, void* d_plain) { return var_base_mul(ctx, srs->s.points, d_pow, n, 0, d_plain, ctx->stream); });
 }
 
 // pts: num_points x 8 limbs in STANDARD (non-Montgomery) form, slot 0 free: sets monomials[0] = G = (1, 2), converts to Montgomery form
@@ -590,14 +632,11 @@ static int srs_from_plain_points(bbg_ctx* ctx, std::vector<uint64_t>& pts, size_
     for (int i = 0; i < 8; i++) pts[i] = 0;
     pts[0] = 1;
     pts[4] = 2;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ScopedMem d_plain;
-    BBG_HIP(hipMalloc(&d_plain.p, num_points * 64));
-    hipError_t e = hipMemcpyAsync(d_plain.p, pts.data(), num_points * 64, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(e, "transcript upload", __FILE__, __LINE__);
-    int rc = field_op_device(1, 5 /* to_montgomery */, d_plain.p, nullptr, d_plain.p, num_points * 2, ctx->stream);
-    if (rc == BBG_OK) rc = make_srs(ctx, d_plain.p, num_points, out);
-    return rc;
+    return srs_from_filled(ctx, num_points, out, [&](void* d_plain) {
+        const hipError_t e = hipMemcpyAsync(d_plain, pts.data(), num_points * 64, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "transcript upload", __FILE__, __LINE__);
+        return field_op_device(1, 5 /* to_montgomery */, d_plain, nullptr, d_plain, num_points * 2, ctx->stream);
+    });
 }
 
 // Ignition transcript reader: restates io::read_transcript_g1 (reference srs/io.cpp:134-162): manifest of seven
@@ -805,10 +844,10 @@ int bbg_srs_lagrange(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, bbg_srs** out)
 {
     CHECK_CTX(ctx);
     if (!srs || !out) { set_error("bbg_srs_lagrange: null argument"); return BBG_E_INVALID; }
-    if (log2n < 1 || log2n > 28) { set_error("bbg_srs_lagrange: log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    if (int rc = check_log2n("bbg_srs_lagrange", log2n, 1, 28)) return rc;
+    if (int rc = check_srs_holds("bbg_srs_lagrange", srs->s, log2n)) return rc;
+    if (int rc = check_srs_device("bbg_srs_lagrange", srs->s, ctx)) return rc;
     const size_t n = (size_t)1 << log2n;
-    if (n > srs->s.n) { set_error("bbg_srs_lagrange: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
-    if (srs->s.device != ctx->device) { set_error("bbg_srs_lagrange: the SRS lives on another device than the context"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     bbg_srs* res = nullptr;
     bool inf = false;
@@ -845,7 +884,7 @@ int bbg_g1_ntt_device(bbg_ctx* ctx, const void* d_points_affine, unsigned log2n,
 {
     CHECK_CTX(ctx);
     if (!d_points_affine || !d_out_affine) { set_error("bbg_g1_ntt_device: null argument"); return BBG_E_INVALID; }
-    if (log2n < 1 || log2n > 28) { set_error("bbg_g1_ntt_device: log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    if (int rc = check_log2n("bbg_g1_ntt_device", log2n, 1, 28)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     int rc = ctx->ecntt_work.ensure(((size_t)1 << log2n) * 128);
     if (rc) return rc;
@@ -856,18 +895,17 @@ int bbg_g1_ntt(bbg_ctx* ctx, const uint64_t* points_affine, unsigned log2n, int 
 {
     CHECK_CTX(ctx);
     if (!points_affine || !out_affine) { set_error("bbg_g1_ntt: null argument"); return BBG_E_INVALID; }
-    if (log2n < 1 || log2n > 28) { set_error("bbg_g1_ntt: log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    if (int rc = check_log2n("bbg_g1_ntt", log2n, 1, 28)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << log2n;
-    int rc = ctx->staging.ensure(n * 64);
-    if (rc == BBG_OK) rc = ctx->ecntt_work.ensure(n * 128);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging.p, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    rc = ecntt_run(ctx, ctx->staging.p, log2n, inverse, ctx->ecntt_work.p, ctx->staging.p, nullptr, ctx->stream); // transformed in place
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, ctx->staging.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_g1_ntt");
+    const auto d_points = st.region(n, 64); // transformed in place
+    BBG_TRY(st.ensure());
+    BBG_TRY(ctx->ecntt_work.ensure(n * 128));
+    BBG_TRY(st.up(d_points, points_affine, n * 64));
+    BBG_TRY(ecntt_run(ctx, st[d_points], log2n, inverse, ctx->ecntt_work.p, st[d_points], nullptr, ctx->stream));
+    BBG_TRY(st.down(out_affine, d_points, n * 64));
+    return st.wait();
 }
 
 // ------------------------------------------------------------------------------------------------ all openings (open_all.hip)
@@ -875,9 +913,9 @@ int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_
 {
     CHECK_CTX(ctx);
     if (!srs || !out) { set_error("bbg_open_all_prepare: null argument"); return BBG_E_INVALID; }
-    if (log2n < 1 || log2n > 27) { set_error("bbg_open_all_prepare: log2n must be 1 .. 27"); return BBG_E_INVALID; }
-    if (((size_t)1 << log2n) > srs->s.n) { set_error("bbg_open_all_prepare: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
-    if (srs->s.device != ctx->device) { set_error("bbg_open_all_prepare: the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    if (int rc = check_log2n("bbg_open_all_prepare", log2n, 1, 27)) return rc;
+    if (int rc = check_srs_holds("bbg_open_all_prepare", srs->s, log2n)) return rc;
+    if (int rc = check_srs_device("bbg_open_all_prepare", srs->s, ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     return open_all_prepare(ctx, srs->s.points, log2n, out);
 }
@@ -887,10 +925,10 @@ int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsig
     if (log2cell == 0) return bbg_open_all_prepare(ctx, srs, log2n, out);
     CHECK_CTX(ctx);
     if (!srs || !out) { set_error("bbg_open_all_prepare_cells: null argument"); return BBG_E_INVALID; }
-    if (log2n < 1 || log2n > 27) { set_error("bbg_open_all_prepare_cells: log2n must be 1 .. 27"); return BBG_E_INVALID; }
+    if (int rc = check_log2n("bbg_open_all_prepare_cells", log2n, 1, 27)) return rc;
     if (log2cell > log2n - 1) { set_error("bbg_open_all_prepare_cells: log2cell must be 0 .. log2n - 1"); return BBG_E_INVALID; }
-    if (((size_t)1 << log2n) > srs->s.n) { set_error("bbg_open_all_prepare_cells: the SRS holds fewer than 2^log2n points"); return BBG_E_INVALID; }
-    if (srs->s.device != ctx->device) { set_error("bbg_open_all_prepare_cells: the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    if (int rc = check_srs_holds("bbg_open_all_prepare_cells", srs->s, log2n)) return rc;
+    if (int rc = check_srs_device("bbg_open_all_prepare_cells", srs->s, ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     return open_cells_prepare(ctx, srs->s.points, log2n, log2cell, out);
 }
@@ -917,15 +955,13 @@ int bbg_open_all(struct bbg_open_all* h, const uint64_t* coeffs, uint64_t* out_a
     CHECK_CTX(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << h->log2n, proofs = n >> h->log2cell;
-    int rc = ctx->staging.ensure(n * 96);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // proofs | coefficients
-    BBG_HIP(hipMemcpyAsync(st + n * 64, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = open_all_run(h, st + n * 64, st, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st, proofs * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_open_all");
+    const auto d_proofs = st.region(n, 64), d_coeffs = st.region(n, 32);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_coeffs, coeffs, n * 32));
+    BBG_TRY(open_all_run(h, st[d_coeffs], st[d_proofs], ctx->stream));
+    BBG_TRY(st.down(out_affine, d_proofs, proofs * 64));
+    return st.wait();
 }
 
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes)
@@ -961,15 +997,13 @@ int bbg_open_all_batch(struct bbg_open_all* h, const uint64_t* coeffs, size_t co
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << h->log2n, proofs = n >> h->log2cell;
     if (count > ((size_t)1 << 40) / n) { set_error("bbg_open_all_batch: count x 2^log2n is out of range"); return BBG_E_INVALID; }
-    int rc = ctx->staging.ensure(count * n * 96);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // proofs | coefficients
-    BBG_HIP(hipMemcpyAsync(st + count * n * 64, coeffs, count * n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = open_all_batch_run(h, st + count * n * 64, count, st, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st, count * proofs * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_open_all_batch");
+    const auto d_proofs = st.region(count * n, 64), d_coeffs = st.region(count * n, 32);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_coeffs, coeffs, count * n * 32));
+    BBG_TRY(open_all_batch_run(h, st[d_coeffs], count, st[d_proofs], ctx->stream));
+    BBG_TRY(st.down(out_affine, d_proofs, count * proofs * 64));
+    return st.wait();
 }
 
 void bbg_open_all_free(struct bbg_open_all* h)
@@ -991,19 +1025,16 @@ int bbg_cells_values(bbg_ctx* ctx, const uint64_t* coeffs, unsigned log2n, unsig
 {
     CHECK_CTX(ctx);
     if (!coeffs || !out) { set_error("bbg_cells_values: null argument"); return BBG_E_INVALID; }
-    int rc = cells_check_shape("bbg_cells_values", log2n, log2cell, count);
-    if (rc) return rc;
+    BBG_TRY(cells_check_shape("bbg_cells_values", log2n, log2cell, count));
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t bytes = count * ((size_t)1 << log2n) * 32;
-    rc = ctx->staging.ensure(2 * bytes);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // coefficients | values
-    BBG_HIP(hipMemcpyAsync(st, coeffs, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = cells_values(ctx, st, log2n, log2cell, count, st + bytes, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out, st + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_cells_values");
+    const auto d_coeffs = st.region(bytes), d_values = st.region(bytes);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_coeffs, coeffs, bytes));
+    BBG_TRY(cells_values(ctx, st[d_coeffs], log2n, log2cell, count, st[d_values], ctx->stream));
+    BBG_TRY(st.down(out, d_values, bytes));
+    return st.wait();
 }
 
 int bbg_cells_recover_device(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* d_values, unsigned log2n, unsigned log2cell, size_t count,
@@ -1019,20 +1050,17 @@ int bbg_cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const ui
 {
     CHECK_CTX(ctx);
     if (!values || !out_coeffs) { set_error("bbg_cells_recover: null argument"); return BBG_E_INVALID; }
-    int rc = cells_check_shape("bbg_cells_recover", log2n, log2cell, count);
-    if (rc == BBG_OK) rc = cells_check_ids("bbg_cells_recover", cell_ids, K, log2n, log2cell);
-    if (rc) return rc;
+    BBG_TRY(cells_check_shape("bbg_cells_recover", log2n, log2cell, count));
+    BBG_TRY(cells_check_ids("bbg_cells_recover", cell_ids, K, log2n, log2cell));
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t in_bytes = count * K * ((size_t)32 << log2cell), out_bytes = count * ((size_t)32 << log2n);
-    rc = ctx->staging.ensure(in_bytes + out_bytes);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // coefficients | values
-    BBG_HIP(hipMemcpyAsync(st + out_bytes, values, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = cells_recover(ctx, cell_ids, K, st + out_bytes, log2n, log2cell, count, st, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_coeffs, st, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_cells_recover");
+    const auto d_coeffs = st.region(out_bytes), d_values = st.region(in_bytes);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_values, values, in_bytes));
+    BBG_TRY(cells_recover(ctx, cell_ids, K, st[d_values], log2n, log2cell, count, st[d_coeffs], ctx->stream));
+    BBG_TRY(st.down(out_coeffs, d_coeffs, out_bytes));
+    return st.wait();
 }
 
 // ------------------------------------------------------------------------------------------------ cell proofs to one pairing check (cells_verify.hip)
@@ -1052,22 +1080,21 @@ int bbg_cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned
 {
     CHECK_CTX(ctx);
     if (!commitments || !values || !proofs || !out) { set_error("bbg_cells_verify_reduce: null argument"); return BBG_E_INVALID; }
-    int rc = cells_verify_check("bbg_cells_verify_reduce", ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho);
-    if (rc) return rc;
+    BBG_TRY(cells_verify_check("bbg_cells_verify_reduce", ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho));
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t com_bytes = ncom * 64, proof_bytes = K * 64, value_bytes = K * ((size_t)32 << log2cell);
-    rc = ctx->staging.ensure(com_bytes + proof_bytes + value_bytes + 256);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // commitments | proofs | values | L, R | the off-curve count
-    char *d_proofs = st + com_bytes, *d_values = d_proofs + proof_bytes, *d_res = d_values + value_bytes;
-    BBG_HIP(hipMemcpyAsync(st, commitments, com_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BBG_HIP(hipMemcpyAsync(d_proofs, proofs, proof_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BBG_HIP(hipMemcpyAsync(d_values, values, value_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = cells_verify_reduce(ctx, srs, log2n, log2cell, st, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, d_res, d_res + 128, ctx->stream);
-    if (rc) return rc;
+    Staged st(ctx, "bbg_cells_verify_reduce");
+    const auto d_com = st.region(com_bytes), d_proofs = st.region(proof_bytes), d_values = st.region(value_bytes);
+    const auto d_res = st.region(256); // L, R (128 B), then the off-curve count: one block, one download
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_com, commitments, com_bytes));
+    BBG_TRY(st.up(d_proofs, proofs, proof_bytes));
+    BBG_TRY(st.up(d_values, values, value_bytes));
+    BBG_TRY(cells_verify_reduce(ctx, srs, log2n, log2cell, st[d_com], ncom, commitment_ids, cell_ids, K, st[d_values], st[d_proofs], rho, st[d_res],
+                                st[d_res] + 128, ctx->stream));
     uint64_t res[18]; // L, R, then the count in the low word of res[16]
-    BBG_HIP(hipMemcpyAsync(res, d_res, 128 + 4, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    BBG_TRY(st.down(res, d_res, 128 + 4));
+    BBG_TRY(st.wait());
     uint32_t off_curve = 0;
     memcpy(&off_curve, res + 16, 4);
     if (off_curve) {
@@ -1125,29 +1152,24 @@ int bbg_msm_batch(bbg_ctx* ctx, bbg_srs* srs, size_t count, const uint64_t* cons
     CHECK_CTX(ctx);
     if (!srs || !scalars || !n || !out_jacobians) { set_error("bbg_msm_batch: null argument"); return BBG_E_INVALID; }
     if (count < 1 || count > BBG_MSM_BATCH_MAX) { set_error("bbg_msm_batch: 1 .. BBG_MSM_BATCH_MAX MSMs per batch"); return BBG_E_INVALID; }
-    size_t zero[BBG_MSM_BATCH_MAX] = { 0 }, total = 0;
-    for (size_t k = 0; k < count; k++) {
+    size_t zero[BBG_MSM_BATCH_MAX] = { 0 };
+    for (size_t k = 0; k < count; k++)
         if (n[k] && !scalars[k]) { set_error("bbg_msm_batch: null scalars"); return BBG_E_INVALID; }
-        total += n[k];
-    }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(total * 32 + 1024);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // results (count x 96 B <= 768 B) | scalars of MSM 0 | MSM 1 | ...
+    Staged st(ctx, "bbg_msm_batch");
+    const auto d_results = st.region(1024); // count x 96 B <= 768 B
+    Staged::Region d_scalars[BBG_MSM_BATCH_MAX];
+    for (size_t k = 0; k < count; k++) d_scalars[k] = st.region(n[k], 32);
+    BBG_TRY(st.ensure());
     const void* d_ptrs[BBG_MSM_BATCH_MAX];
-    size_t at = 1024;
     for (size_t k = 0; k < count; k++) {
-        d_ptrs[k] = st + at;
-        if (n[k]) BBG_HIP(hipMemcpyAsync(st + at, scalars[k], n[k] * 32, hipMemcpyHostToDevice, ctx->stream));
-        at += n[k] * 32;
+        d_ptrs[k] = st[d_scalars[k]];
+        if (n[k]) BBG_TRY(st.up(d_scalars[k], scalars[k], n[k] * 32));
     }
-    rc = msm_run_batch(ctx, srs->s, (int)count, d_ptrs, from ? from : zero, n, st, ctx->stream);
-    if (rc) return rc;
-    rc = msm_join(ctx, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_jacobians, st, count * 96, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    BBG_TRY(msm_run_batch(ctx, srs->s, (int)count, d_ptrs, from ? from : zero, n, st[d_results], ctx->stream));
+    BBG_TRY(msm_join(ctx, ctx->stream));
+    BBG_TRY(st.down(out_jacobians, d_results, count * 96));
+    return st.wait();
 }
 
 int bbg_msm_plan(bbg_ctx* ctx, const bbg_srs* srs, size_t n, int* window_bits, int* windows)
@@ -1168,16 +1190,13 @@ int bbg_msm(bbg_ctx* ctx, bbg_srs* srs, const uint64_t* scalars, size_t from, si
     CHECK_CTX(ctx);
     if (!srs || (!scalars && n) || !out_jacobian) { set_error("bbg_msm: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(n * 32 + 256);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p;
-    rc = msm_run(ctx, srs->s, st + 256, from, n, st, ctx->stream, scalars); // uploads the scalars itself, in pieces, under its first pass
-    if (rc) return rc;
-    rc = msm_join(ctx, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_jacobian, st, 96, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_msm");
+    const auto d_result = st.region(256), d_scalars = st.region(n, 32);
+    BBG_TRY(st.ensure());
+    BBG_TRY(msm_run(ctx, srs->s, st[d_scalars], from, n, st[d_result], ctx->stream, scalars)); // uploads the scalars itself, in pieces, under its first pass
+    BBG_TRY(msm_join(ctx, ctx->stream));
+    BBG_TRY(st.down(out_jacobian, d_result, 96));
+    return st.wait();
 }
 
 int bbg_g1_sum(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t out_jacobian[12])
@@ -1185,15 +1204,13 @@ int bbg_g1_sum(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t out_j
     CHECK_CTX(ctx);
     if ((!jacobians && n) || !out_jacobian) { set_error("bbg_g1_sum: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(n * 96 + 256);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p;
-    if (n) BBG_HIP(hipMemcpyAsync(st + 256, jacobians, n * 96, hipMemcpyHostToDevice, ctx->stream));
-    rc = g1_sum_device(ctx, st + 256, n, st, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_jacobian, st, 96, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_g1_sum");
+    const auto d_result = st.region(256), d_terms = st.region(n, 96);
+    BBG_TRY(st.ensure());
+    if (n) BBG_TRY(st.up(d_terms, jacobians, n * 96));
+    BBG_TRY(g1_sum_device(ctx, st[d_terms], n, st[d_result], ctx->stream));
+    BBG_TRY(st.down(out_jacobian, d_result, 96));
+    return st.wait();
 }
 
 int bbg_g1_sum_device(bbg_ctx* ctx, const void* d_jacobians, size_t n, void* d_out_jacobian)
@@ -1210,15 +1227,13 @@ int bbg_g1_normalize(bbg_ctx* ctx, const uint64_t* jacobians, size_t n, uint64_t
     if ((!jacobians || !out_affine) && n) { set_error("bbg_g1_normalize: null argument"); return BBG_E_INVALID; }
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(n * 160);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p;
-    BBG_HIP(hipMemcpyAsync(st, jacobians, n * 96, hipMemcpyHostToDevice, ctx->stream));
-    rc = g1_normalize_device(st, n, st + n * 96, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st + n * 96, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_g1_normalize");
+    const auto d_jacs = st.region(n, 96), d_affine = st.region(n, 64);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_jacs, jacobians, n * 96));
+    BBG_TRY(g1_normalize_device(st[d_jacs], n, st[d_affine], ctx->stream));
+    BBG_TRY(st.down(out_affine, d_affine, n * 64));
+    return st.wait();
 }
 
 int bbg_g1_fixed_base_mul_device(bbg_ctx* ctx, const uint64_t* base_affine, const void* d_scalars, size_t n, void* d_out_affine)
@@ -1234,15 +1249,14 @@ int bbg_g1_fixed_base_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint6
     CHECK_CTX(ctx);
     if ((!scalars || !out_affine) && n) { set_error("bbg_g1_fixed_base_mul: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(n * 96 + 64);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // scalars | results
-    if (n) BBG_HIP(hipMemcpyAsync(st, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = fixed_base_mul(ctx, base_affine, st, n, st + n * 32, ctx->stream); // validates the base for n = 0 as well
+    Staged st(ctx, "bbg_g1_fixed_base_mul");
+    const auto d_scalars = st.region(n, 32), d_results = st.region(n + 1, 64); // one point of slack behind the results
+    BBG_TRY(st.ensure());
+    if (n) BBG_TRY(st.up(d_scalars, scalars, n * 32));
+    const int rc = fixed_base_mul(ctx, base_affine, st[d_scalars], n, st[d_results], ctx->stream); // validates the base for n = 0 as well
     if (rc || n == 0) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st + n * 32, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    BBG_TRY(st.down(out_affine, d_results, n * 64));
+    return st.wait();
 }
 
 int bbg_g1_batch_mul_device(bbg_ctx* ctx, const void* d_points_affine, const void* d_scalars, size_t n, int one_scalar, void* d_out_affine)
@@ -1260,16 +1274,14 @@ int bbg_g1_batch_mul(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t ns = one_scalar ? 1 : n;
-    int rc = ctx->staging.ensure(n * 64 + ns * 32);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // points (multiplied in place) | scalars
-    BBG_HIP(hipMemcpyAsync(st, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    BBG_HIP(hipMemcpyAsync(st + n * 64, scalars, ns * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = var_base_mul(ctx, st, st + n * 64, n, one_scalar, st, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_g1_batch_mul");
+    const auto d_points = st.region(n, 64), d_scalars = st.region(ns, 32); // the points are multiplied in place
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_points, points_affine, n * 64));
+    BBG_TRY(st.up(d_scalars, scalars, ns * 32));
+    BBG_TRY(var_base_mul(ctx, st[d_points], st[d_scalars], n, one_scalar, st[d_points], ctx->stream));
+    BBG_TRY(st.down(out_affine, d_points, n * 64));
+    return st.wait();
 }
 
 int bbg_g1_msm_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries)
@@ -1290,18 +1302,16 @@ int bbg_g1_msm(bbg_ctx* ctx, const uint64_t* points_affine, const uint64_t* scal
     if (!out_affine || (n && (!points_affine || !scalars))) { set_error("bbg_g1_msm: null argument"); return BBG_E_INVALID; }
     if (int rc = msm_points_plan(n, window_bits, nullptr, nullptr, nullptr, nullptr)) return rc; // before the staging buffer is sized by n
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(64 + n * 96);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // result | points | scalars
+    Staged st(ctx, "bbg_g1_msm");
+    const auto d_result = st.region(64), d_points = st.region(n, 64), d_scalars = st.region(n, 32);
+    BBG_TRY(st.ensure());
     if (n) {
-        BBG_HIP(hipMemcpyAsync(st + 64, points_affine, n * 64, hipMemcpyHostToDevice, ctx->stream));
-        BBG_HIP(hipMemcpyAsync(st + 64 + n * 64, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+        BBG_TRY(st.up(d_points, points_affine, n * 64));
+        BBG_TRY(st.up(d_scalars, scalars, n * 32));
     }
-    rc = msm_points_run(ctx, st + 64, st + 64 + n * 64, n, window_bits, st, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out_affine, st, 64, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    BBG_TRY(msm_points_run(ctx, st[d_points], st[d_scalars], n, window_bits, st[d_result], ctx->stream));
+    BBG_TRY(st.down(out_affine, d_result, 64));
+    return st.wait();
 }
 
 // ------------------------------------------------------------------------------------------------ G2 and the pairing (pairing.hip)
@@ -1343,17 +1353,15 @@ int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t*
     if (int rc = pairing_product_check("bbg_pairing_product", ctx, lines, g1_affine, count, out_fq12, status)) return rc; // before the staging buffer is sized by count
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t in_bytes = count * lines->pairs * 64;
-    int rc = ctx->staging.ensure(count * 388 + in_bytes);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p; // values | points | status
-    char *d_in = st + count * 384, *d_flags = d_in + in_bytes;
-    BBG_HIP(hipMemcpyAsync(d_in, g1_affine, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = pairing_product_run(ctx, lines, d_in, count, st, d_flags, ctx->stream);
-    if (rc) return rc;
+    Staged st(ctx, "bbg_pairing_product");
+    const auto d_values = st.region(count, 384), d_points = st.region(in_bytes), d_flags = st.region(count, 4);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_points, g1_affine, in_bytes));
+    BBG_TRY(pairing_product_run(ctx, lines, st[d_points], count, st[d_values], st[d_flags], ctx->stream));
     std::vector<uint32_t> flags(count);
-    BBG_HIP(hipMemcpyAsync(flags.data(), d_flags, count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_fq12) BBG_HIP(hipMemcpyAsync(out_fq12, st, count * 384, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    BBG_TRY(st.down(flags.data(), d_flags, count * 4));
+    if (out_fq12) BBG_TRY(st.down(out_fq12, d_values, count * 384));
+    BBG_TRY(st.wait());
     if (status) memcpy(status, flags.data(), count * 4);
     const size_t off_curve = (size_t)std::count(flags.begin(), flags.end(), 2u);
     if (off_curve) {
@@ -1393,14 +1401,13 @@ int bbg_ntt(bbg_ctx* ctx, uint64_t* coeffs, unsigned log2n, int op, size_t gener
     if (log2n > 28) { set_error("bbg_ntt: log2n > 28 exceeds the 2-adicity of BN254 Fr (fr.hpp:27-30)"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t bytes = ((size_t)1 << log2n) * 32;
-    int rc = ctx->staging.ensure(bytes);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging.p, coeffs, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = ntt_run(ctx, ctx->staging.p, log2n, op, generator_size, constant, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(coeffs, ctx->staging.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_ntt");
+    const auto d_coeffs = st.region(bytes); // transformed in place
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_coeffs, coeffs, bytes));
+    BBG_TRY(ntt_run(ctx, st[d_coeffs], log2n, op, generator_size, constant, ctx->stream));
+    BBG_TRY(st.down(coeffs, d_coeffs, bytes));
+    return st.wait();
 }
 
 int bbg_scale_powers_device(bbg_ctx* ctx, void* d_a, size_t count, const uint64_t* start, const uint64_t* base)
@@ -1470,14 +1477,13 @@ int bbg_coset_fft_extend(bbg_ctx* ctx, const uint64_t* coeffs, unsigned log2n, u
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << log2n, m = (size_t)1 << log2_domain;
-    // n coefficients land behind the m-element result area; the transform reads them zero-extended and writes the result area
-    int rc = ctx->staging.ensure((m + n) * 32);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync((char*)ctx->staging.p + m * 32, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = ntt_coset_extend(ctx, (char*)ctx->staging.p + m * 32, n, ctx->staging.p, log2_domain, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out, ctx->staging.p, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
+    Staged st(ctx, "bbg_coset_fft_extend");
+    const auto d_result = st.region(m, 32), d_coeffs = st.region(n, 32); // the transform reads the coefficients zero-extended and writes the result area
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_coeffs, coeffs, n * 32));
+    BBG_TRY(ntt_coset_extend(ctx, st[d_coeffs], n, st[d_result], log2_domain, ctx->stream));
+    BBG_TRY(st.down(out, d_result, m * 32));
+    BBG_TRY(st.wait());
     memcpy(out + m * 4, out, 4 * 32); // add_lagrange_base_coefficient(out[0..3])
     return BBG_OK;
 }
@@ -1489,14 +1495,13 @@ int bbg_coset_fft_split(bbg_ctx* ctx, uint64_t* coeffs, unsigned log2n, size_t e
     if (ext == 0 || log2n > 28 || ext > ((size_t)1 << 28)) { set_error("bbg_coset_fft_split: bad size"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t n = (size_t)1 << log2n;
-    int rc = ctx->staging.ensure(n * ext * 32);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = ntt_coset_split(ctx, ctx->staging.p, log2n, ext, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(coeffs, ctx->staging.p, n * ext * 32, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_coset_fft_split");
+    const auto d_coeffs = st.region(n * ext, 32); // n coefficients in, n * ext values out, in place
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_coeffs, coeffs, n * 32));
+    BBG_TRY(ntt_coset_split(ctx, st[d_coeffs], log2n, ext, ctx->stream));
+    BBG_TRY(st.down(coeffs, d_coeffs, n * ext * 32));
+    return st.wait();
 }
 
 // ------------------------------------------------------------------------------------------------ polynomial helpers
@@ -1524,26 +1529,24 @@ int bbg_poly_evaluate(bbg_ctx* ctx, const uint64_t* coeffs, size_t n, const uint
     CHECK_CTX(ctx);
     if ((!coeffs && n) || !z || !out) { set_error("bbg_poly_evaluate: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(n * 32 + 32);
-    if (rc) return rc;
-    if (n) BBG_HIP(hipMemcpyAsync(ctx->staging.p, coeffs, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    return poly_evaluate(ctx, ctx->staging.p, n, z, out, ctx->stream);
+    Staged st(ctx, "bbg_poly_evaluate");
+    const auto d_coeffs = st.region(n + 1, 32); // one element of slack
+    BBG_TRY(st.ensure());
+    if (n) BBG_TRY(st.up(d_coeffs, coeffs, n * 32));
+    return poly_evaluate(ctx, st[d_coeffs], n, z, out, ctx->stream); // downloads the value and waits itself
 }
 int bbg_kate_opening(bbg_ctx* ctx, const uint64_t* src, uint64_t* dest, size_t n, const uint64_t z[4], uint64_t f_out[4])
 {
     CHECK_CTX(ctx);
     if ((n && (!src || !dest)) || !z || !f_out) { set_error("bbg_kate_opening: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(2 * n * 32 + 64);
-    if (rc) return rc;
-    char* d_src = (char*)ctx->staging.p;
-    char* d_dest = d_src + n * 32 + 32;
-    if (n) BBG_HIP(hipMemcpyAsync(d_src, src, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = poly_kate_opening(ctx, d_src, d_dest, n, z, f_out, ctx->stream);
-    if (rc) return rc;
-    if (n) BBG_HIP(hipMemcpyAsync(dest, d_dest, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_kate_opening");
+    const auto d_src = st.region(n + 1, 32), d_dest = st.region(n + 1, 32); // one element of slack behind each
+    BBG_TRY(st.ensure());
+    if (n) BBG_TRY(st.up(d_src, src, n * 32));
+    BBG_TRY(poly_kate_opening(ctx, st[d_src], st[d_dest], n, z, f_out, ctx->stream));
+    if (n) BBG_TRY(st.down(dest, d_dest, n * 32));
+    return st.wait();
 }
 int bbg_fr_batch_invert_device(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n)
 {
@@ -1563,12 +1566,12 @@ int bbg_poly_evaluate_lagrange(bbg_ctx* ctx, const uint64_t* evals, unsigned log
     CHECK_CTX(ctx);
     if (!evals || !z || !out || log2n == 0 || log2n > 28) { set_error("bbg_poly_evaluate_lagrange: bad argument (1 <= log2n <= 28)"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t bytes = ((size_t)1 << log2n) * 32;
-    int rc = ctx->staging.ensure(bytes);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging.p, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
-    const void* d_evals = ctx->staging.p;
-    return poly_evaluate_lagrange(ctx, &d_evals, nullptr, 1, log2n, z, out, ctx->stream);
+    Staged st(ctx, "bbg_poly_evaluate_lagrange");
+    const auto d_values = st.region((size_t)32 << log2n);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_values, evals, (size_t)32 << log2n));
+    const void* d_evals = st[d_values];
+    return poly_evaluate_lagrange(ctx, &d_evals, nullptr, 1, log2n, z, out, ctx->stream); // downloads the value and waits itself
 }
 int bbg_kate_opening_lagrange_device(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t z[4], uint64_t f_out[4])
 {
@@ -1583,14 +1586,13 @@ int bbg_divide_by_pseudo_vanishing(bbg_ctx* ctx, uint64_t* evals, unsigned log2_
     if (log2_target > 28) { set_error("bbg_divide_by_pseudo_vanishing: log2_target > 28"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t bytes = ((size_t)1 << log2_target) * 32;
-    int rc = ctx->staging.ensure(bytes);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(ctx->staging.p, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = poly_divide_pseudo_vanishing(ctx, ctx->staging.p, log2_src, log2_target, num_roots_cut, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(evals, ctx->staging.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_divide_by_pseudo_vanishing");
+    const auto d_evals = st.region(bytes); // divided in place
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_evals, evals, bytes));
+    BBG_TRY(poly_divide_pseudo_vanishing(ctx, st[d_evals], log2_src, log2_target, num_roots_cut, ctx->stream));
+    BBG_TRY(st.down(evals, d_evals, bytes));
+    return st.wait();
 }
 int bbg_divide_by_pseudo_vanishing_device(bbg_ctx* ctx, void* d_evals, unsigned log2_src, unsigned log2_target, size_t num_roots_cut)
 {
@@ -1605,16 +1607,14 @@ int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint6
     if (!a || !out) { set_error("bbg_field_op: null argument"); return BBG_E_INVALID; }
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    int rc = ctx->staging.ensure(n * 96);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p;
-    BBG_HIP(hipMemcpyAsync(st, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    if (b) BBG_HIP(hipMemcpyAsync(st + n * 32, b, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    rc = field_op_device(which, op, st, b ? st + n * 32 : nullptr, st + n * 64, n, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out, st + n * 64, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_field_op");
+    const auto d_a = st.region(n, 32), d_b = st.region(n, 32), d_out = st.region(n, 32);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_a, a, n * 32));
+    if (b) BBG_TRY(st.up(d_b, b, n * 32));
+    BBG_TRY(field_op_device(which, op, st[d_a], b ? st[d_b] : nullptr, st[d_out], n, ctx->stream));
+    BBG_TRY(st.down(out, d_out, n * 32));
+    return st.wait();
 }
 
 int bbg_limb29_op_shape(int which, int op, int* operands, int* results)
@@ -1634,15 +1634,13 @@ int bbg_limb29_op(bbg_ctx* ctx, int which, int op, const uint32_t* in, size_t n,
     if (!in || !out) { set_error("bbg_limb29_op: null argument"); return BBG_E_INVALID; }
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t in_bytes = n * operands * 36, out_bytes = n * results * 36; // rows of 9 words
-    int rc = ctx->staging.ensure(in_bytes + out_bytes);
-    if (rc) return rc;
-    char* st = (char*)ctx->staging.p;
-    BBG_HIP(hipMemcpyAsync(st, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = limb29_op_device(which, op, st, st + in_bytes, n, ctx->stream);
-    if (rc) return rc;
-    BBG_HIP(hipMemcpyAsync(out, st + in_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BBG_HIP(hipStreamSynchronize(ctx->stream));
-    return BBG_OK;
+    Staged st(ctx, "bbg_limb29_op");
+    const auto d_in = st.region(in_bytes), d_out = st.region(out_bytes);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_in, in, in_bytes));
+    BBG_TRY(limb29_op_device(which, op, st[d_in], st[d_out], n, ctx->stream));
+    BBG_TRY(st.down(out, d_out, out_bytes));
+    return st.wait();
 }
 
 } // extern "C"

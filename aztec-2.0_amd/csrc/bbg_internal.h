@@ -16,6 +16,12 @@ namespace bbg {
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
+struct Srs;
+// Argument checks shared by the entry points (bbg_capi.hip): BBG_OK, or BBG_E_INVALID with the error text set to "<who>: " and the sentence
+int check_log2n(const char* who, unsigned log2n, unsigned lo, unsigned hi);                         // "log2n must be <lo> .. <hi>"
+int check_srs_holds(const char* who, const Srs& srs, unsigned log2, const char* name = "log2n");    // "the SRS holds fewer than 2^<name> points"
+int check_srs_device(const char* who, const Srs& srs, const bbg_ctx* ctx, const char* hint = "");   // "the SRS lives on another device than the context<hint>"
+int check_fr_nonzero(const char* who, const uint64_t v[4], const char* what);                       // v is 0 or r, the two forms of zero in [0, 2r): <what>
 
 #define BBG_HIP(expr)                                                                                                \
     do {                                                                                                             \
@@ -25,6 +31,13 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 // blocks of `block` threads that cover n items
 static inline int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
+
+// the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+static inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const char *x = (const char*)a, *y = (const char*)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
 
 // A grow-only device buffer: the one owner type of a context's (and a bbg_multi's) working memory.  No destructor frees it: its owner
 // is torn down explicitly (bbg_destroy, bbg_memory_trim) after hipSetDevice.

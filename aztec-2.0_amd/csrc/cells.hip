@@ -130,11 +130,6 @@ __global__ void __launch_bounds__(256) k_cells_divide(Fr* b, size_t n, unsigned 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *x = (const char*)a, *y = (const char*)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
 static unsigned transpose_grid(unsigned log2r, unsigned log2l)
 {
     const size_t r = (size_t)1 << log2r, l = (size_t)1 << log2l;
@@ -144,7 +139,7 @@ static unsigned sweep_grid(size_t n) { return (unsigned)std::min<size_t>((n + 25
 
 int cells_check_shape(const char* who, unsigned log2n, unsigned log2cell, size_t count)
 {
-    if (log2n < 1 || log2n > 28) { set_error(std::string(who) + ": log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    if (int rc = check_log2n(who, log2n, 1, 28)) return rc;
     if (log2cell > log2n - 1) { set_error(std::string(who) + ": log2cell must be 0 .. log2n - 1"); return BBG_E_INVALID; }
     if (count < 1 || count > (size_t)BARY_MAX) { set_error(std::string(who) + ": count must be 1 .. 32"); return BBG_E_INVALID; }
     return BBG_OK;

@@ -91,31 +91,6 @@ __global__ void __launch_bounds__(256) k_cv_scale(Fr* a, size_t l, unsigned log2
 }
 
 // ---------------------------------------------------------------------------------------------- G1 side
-// y^2 = x^3 + 3 for a finite point with coordinates in [0, 2p)
-__device__ __forceinline__ bool aff_on_curve(const Affine& a)
-{
-    const Fq three = fe_add(fe_dbl(Fq::one()), Fq::one());
-    return fe_eq(fe_sqr(a.y), fe_add(fe_mul(fe_sqr(a.x), a.x), three));
-}
-
-// the sum of `v` over the 64 lanes of the wave, in every lane.  Every lane of the wave must call it.
-__device__ __forceinline__ Xyzz wave_sum(Xyzz v)
-{
-#pragma unroll 1
-    for (int d = 32; d >= 1; d >>= 1) {
-        Xyzz o;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            o.x.v[w] = (uint32_t)__shfl_xor((int)v.x.v[w], d, 64);
-            o.y.v[w] = (uint32_t)__shfl_xor((int)v.y.v[w], d, 64);
-            o.zz.v[w] = (uint32_t)__shfl_xor((int)v.zz.v[w], d, 64);
-            o.zzz.v[w] = (uint32_t)__shfl_xor((int)v.zzz.v[w], d, 64);
-        }
-        v = xyzz_add(v, o);
-    }
-    return v;
-}
-
 // Item i < K: prod[i] = pw[k] proofs[k], k = perm[i] (group order); item K + c: com_out[c] = W[c] commitments[c].  A finite point off the
 // curve is counted in *bad and taken as infinity.  The shape of k_open_all_pointwise: blocks of one wave, two waves per SIMD, lane tables.
 __global__ void __launch_bounds__(64, 2) k_cv_mul(const Affine* __restrict__ proofs, const Fr* __restrict__ pw, const uint32_t* __restrict__ perm, size_t K,
@@ -151,7 +126,7 @@ __global__ void __launch_bounds__(64) k_cv_segsum(const Xyzz* __restrict__ prod,
         Xyzz acc = xyzz_inf();
 #pragma unroll 1
         for (size_t j = (size_t)b + lane; j < e; j += 64) acc = xyzz_add(acc, xyzz_load(prod + j));
-        if (e - b > 1) acc = wave_sum(acc);
+        if (e - b > 1) acc = xyzz_wave_sum(acc);
         if (lane == 0) xyzz_store(S + m, acc);
     }
 }
@@ -180,7 +155,7 @@ __global__ void __launch_bounds__(64) k_cv_reduce(const Xyzz* __restrict__ a0, s
     Xyzz acc = xyzz_inf();
 #pragma unroll 1
     for (size_t i = (size_t)blockIdx.x * 64 + threadIdx.x; i < n; i += (size_t)gridDim.x * 64) acc = xyzz_add(acc, xyzz_load(a + i));
-    acc = wave_sum(acc);
+    acc = xyzz_wave_sum(acc);
     if (threadIdx.x == 0) xyzz_store(parts + (size_t)blockIdx.y * CV_PARTS + blockIdx.x, acc);
 }
 
@@ -195,8 +170,8 @@ __global__ void __launch_bounds__(64) k_cv_finish(const Xyzz* __restrict__ parts
     for (unsigned i = lane; i < np; i += 64) L = xyzz_add(L, xyzz_load(parts + i));
 #pragma unroll 1
     for (unsigned i = lane; i < np; i += 64) R = xyzz_add(R, xyzz_load(parts + CV_PARTS + i));
-    L = wave_sum(L);
-    R = wave_sum(R);
+    L = xyzz_wave_sum(L);
+    R = xyzz_wave_sum(R);
     if (lane != 0) return;
     Jacobian j;
     j.x = fe_load<FqP>(&msm_a->x);
@@ -208,23 +183,17 @@ __global__ void __launch_bounds__(64) k_cv_finish(const Xyzz* __restrict__ parts
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static bool cv_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *x = (const char*)a, *y = (const char*)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 int cells_verify_check(const char* who, const bbg_ctx* ctx, const bbg_srs* srs, unsigned log2n, unsigned log2cell, size_t ncom, const uint32_t* commitment_ids,
                        const uint32_t* cell_ids, size_t K, const uint64_t* rho)
 {
     const std::string w(who);
     if (!srs || !commitment_ids || !cell_ids || !rho) { set_error(w + ": null argument"); return BBG_E_INVALID; }
-    if (log2n < 1 || log2n > 28) { set_error(w + ": log2n must be 1 .. 28"); return BBG_E_INVALID; }
+    if (int rc = check_log2n(who, log2n, 1, 28)) return rc;
     if (log2cell > log2n - 1) { set_error(w + ": log2cell must be 0 .. log2n - 1"); return BBG_E_INVALID; }
     if (K < 1 || K > CV_MAX) { set_error(w + ": K must be 1 .. 2^30"); return BBG_E_INVALID; }
     if (ncom < 1 || ncom > CV_MAX) { set_error(w + ": ncom must be 1 .. 2^30"); return BBG_E_INVALID; }
-    if (((size_t)1 << log2cell) > srs->s.n) { set_error(w + ": the SRS holds fewer than 2^log2cell points"); return BBG_E_INVALID; }
-    if (srs->s.device != ctx->device) { set_error(w + ": the SRS lives on another device than the context"); return BBG_E_INVALID; }
+    if (int rc = check_srs_holds(who, srs->s, log2cell, "log2cell")) return rc;
+    if (int rc = check_srs_device(who, srs->s, ctx)) return rc;
     const size_t r = (size_t)1 << (log2n - log2cell);
     for (size_t k = 0; k < K; k++) {
         if (cell_ids[k] >= r) { set_error(w + ": a cell id is not below r = n / l"); return BBG_E_INVALID; }
@@ -255,11 +224,11 @@ int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log
     const size_t n = (size_t)1 << log2n, l = (size_t)1 << log2cell, r = (size_t)1 << log2r;
     const struct { const void* p; size_t bytes; } ins[3] = { { d_commitments, ncom * 64 }, { d_values, K * l * 32 }, { d_proofs, K * 64 } };
     for (const auto& in : ins)
-        if (cv_overlap(d_out, 128, in.p, in.bytes) || (d_off_curve && cv_overlap(d_off_curve, 4, in.p, in.bytes))) {
+        if (ranges_overlap(d_out, 128, in.p, in.bytes) || (d_off_curve && ranges_overlap(d_off_curve, 4, in.p, in.bytes))) {
             set_error(std::string(who) + ": an output overlaps an input");
             return BBG_E_INVALID;
         }
-    if (d_off_curve && cv_overlap(d_off_curve, 4, d_out, 128)) { set_error(std::string(who) + ": the two outputs overlap"); return BBG_E_INVALID; }
+    if (d_off_curve && ranges_overlap(d_off_curve, 4, d_out, 128)) { set_error(std::string(who) + ": the two outputs overlap"); return BBG_E_INVALID; }
     void* dc = nullptr;
     if (int rc = ntt_domain_consts(ctx, log2n, &dc)) return rc;
     // working memory, all of it sized before the first launch: the lanes' tables, then

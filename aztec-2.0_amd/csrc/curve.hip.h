@@ -176,6 +176,29 @@ __device__ __forceinline__ Xyzz xyzz_add(const Xyzz& a, const Xyzz& b)
     r.zzz = fe_mul(fe_mul(a.zzz, b.zzz), PPP);
     return r;
 }
+// the sum of `v` over the 64 lanes of the wave, in every lane.  Every lane of the wave must call it.
+__device__ __forceinline__ Xyzz xyzz_wave_sum(Xyzz v)
+{
+#pragma unroll 1
+    for (int d = 32; d >= 1; d >>= 1) {
+        Xyzz o;
+#pragma unroll
+        for (int w = 0; w < 8; w++) {
+            o.x.v[w] = (uint32_t)__shfl_xor((int)v.x.v[w], d, 64);
+            o.y.v[w] = (uint32_t)__shfl_xor((int)v.y.v[w], d, 64);
+            o.zz.v[w] = (uint32_t)__shfl_xor((int)v.zz.v[w], d, 64);
+            o.zzz.v[w] = (uint32_t)__shfl_xor((int)v.zzz.v[w], d, 64);
+        }
+        v = xyzz_add(v, o);
+    }
+    return v;
+}
+// y^2 = x^3 + 3 for a finite point with coordinates in [0, 2p)
+__device__ __forceinline__ bool aff_on_curve(const Affine& a)
+{
+    const Fq three = fe_add(fe_dbl(Fq::one()), Fq::one());
+    return fe_eq(fe_sqr(a.y), fe_add(fe_mul(fe_sqr(a.x), a.x), three));
+}
 // XYZZ -> the reference's Jacobian (X', Y', Z') with x = X'/Z'^2, y = Y'/Z'^3: take Z' = ZZ*ZZZ.
 __device__ __forceinline__ Jacobian xyzz_to_jacobian(const Xyzz& p)
 {

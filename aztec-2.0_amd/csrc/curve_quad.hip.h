@@ -171,4 +171,30 @@ __device__ __forceinline__ Xyzz quad_sum4(const Xyzz& p, int q)
     return xyzz_add_q4(a, b, q);
 }
 
+// ---------------------------------------------------------------------------------- block reductions of the MSM's reduce phase
+// LDS tree reduction of one point per thread; result valid in thread 0.
+static __device__ Xyzz block_reduce(Xyzz v, Xyzz* sm, int nthreads)
+{
+    const int tid = threadIdx.x;
+    for (int stride = nthreads >> 1; stride >= 1; stride >>= 1) {
+        if (tid >= stride && tid < 2 * stride) sm[tid - stride] = v;
+        __syncthreads();
+        if (tid < stride) v = xyzz_add(v, sm[tid]);
+        __syncthreads();
+    }
+    return v;
+}
+// the same over `nlogical` logical lanes of four threads each (lt = thread / 4, q = thread % 4): every addition shared by a quad
+__device__ __forceinline__ Xyzz block_reduce_q4(Xyzz v, Xyzz* sm, int nlogical)
+{
+    const int lt = threadIdx.x >> 2, q = threadIdx.x & 3;
+    for (int stride = nlogical >> 1; stride >= 1; stride >>= 1) {
+        if (q == 0 && lt >= stride && lt < 2 * stride) sm[lt - stride] = v;
+        __syncthreads();
+        if (lt < stride) v = xyzz_add_q4(v, sm[lt], q);
+        __syncthreads();
+    }
+    return v;
+}
+
 } // namespace bbg

@@ -96,30 +96,7 @@ __global__ void __launch_bounds__(128) k_srs_hashed(Affine* out, size_t n, uint6
     for (int e = cnt - 1; e >= 0; e--) aff_batch_finish(out + i0 + e, fin[e], zw[e], prefix[e], inv, aff_inf());
 }
 
-// ---------------------------------------------------------------------------------- last reduce stage, g1 helpers
-// LDS tree reduction of one point per thread; result valid in thread 0.
-static __device__ Xyzz block_reduce(Xyzz v, Xyzz* sm, int nthreads)
-{
-    const int tid = threadIdx.x;
-    for (int stride = nthreads >> 1; stride >= 1; stride >>= 1) {
-        if (tid >= stride && tid < 2 * stride) sm[tid - stride] = v;
-        __syncthreads();
-        if (tid < stride) v = xyzz_add(v, sm[tid]);
-        __syncthreads();
-    }
-    return v;
-}
-static __device__ __forceinline__ Xyzz block_reduce_q4(Xyzz v, Xyzz* sm, int nlogical)
-{
-    const int lt = threadIdx.x >> 2, q = threadIdx.x & 3;
-    for (int stride = nlogical >> 1; stride >= 1; stride >>= 1) {
-        if (q == 0 && lt >= stride && lt < 2 * stride) sm[lt - stride] = v;
-        __syncthreads();
-        if (lt < stride) v = xyzz_add_q4(v, sm[lt], q);
-        __syncthreads();
-    }
-    return v;
-}
+// ---------------------------------------------------------------------------------- last reduce stage, g1 helpers (block_reduce[_q4]: curve_quad.hip.h)
 __global__ void __launch_bounds__(64, 1) k_final_sum(const Xyzz* __restrict__ planes, int nplanes, Jacobian* out)
 {
     __shared__ Xyzz sm[16];

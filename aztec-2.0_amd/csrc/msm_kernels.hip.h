@@ -789,7 +789,6 @@ k_accumulate29(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ o
 }
 
 // one block per queued bucket: the bucket's sum from its entries, complete formulas (grid-stride over the queue; empty in all but degenerate inputs)
-static __device__ Xyzz block_reduce(Xyzz v, Xyzz* sm, int nthreads);
 template <int C> __global__ void __launch_bounds__(256)
 k_redo(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ offsets, const Affine* __restrict__ table, size_t n_srs, RedoQueue rq, Xyzz* buckets)
 {
@@ -872,8 +871,6 @@ k_combine(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __rest
         xyzz_store(buckets + (b - 1), acc);
     }
 }
-
-static __device__ Xyzz block_reduce(Xyzz v, Xyzz* sm, int nthreads);
 
 __device__ __forceinline__ Xyzz xyzz_shfl_xor(const Xyzz& v, int mask)
 {
@@ -960,19 +957,6 @@ k_combine_long(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* _
     }
 }
 
-// LDS tree reduction of one point per thread; result valid in thread 0.
-static __device__ Xyzz block_reduce(Xyzz v, Xyzz* sm, int nthreads)
-{
-    const int tid = threadIdx.x;
-    for (int stride = nthreads >> 1; stride >= 1; stride >>= 1) {
-        if (tid >= stride && tid < 2 * stride) sm[tid - stride] = v;
-        __syncthreads();
-        if (tid < stride) v = xyzz_add(v, sm[tid]);
-        __syncthreads();
-    }
-    return v;
-}
-
 // weight of bucket index idx (0-based) is idx + 1 = hi*COLS + lo + 1  (COLS = 2^log_cols, ROWS = 2^log_rows).
 // blocks 0..ROWS-1: Row_hi = sum_lo B[hi][lo] ; blocks ROWS..ROWS+COLS-1: Col_lo = sum_hi B[hi][lo].
 template <int C> __global__ void __launch_bounds__(256, 1) k_rowcol(const Xyzz* __restrict__ buckets, Xyzz* rows, Xyzz* cols)
@@ -1028,18 +1012,7 @@ template <int C> __global__ void __launch_bounds__(256, 1) k_final_planes(const 
 // ------------------------------------------------------------------------------------ quad-cooperative reduce phase
 // The same reduce phase with every EC operation shared by FOUR adjacent lanes (curve_quad.hip.h): a logical lane lt = thread / 4,
 // q = thread % 4.  Identical structure and results; the dependency chain is ~3x shorter in time.  Blocks carry 4x the threads for the
-// same number of logical lanes (512 threads = 128 logical lanes, so that a thread may keep up to 256 VGPRs).
-__device__ __forceinline__ Xyzz block_reduce_q4(Xyzz v, Xyzz* sm, int nlogical)
-{
-    const int lt = threadIdx.x >> 2, q = threadIdx.x & 3;
-    for (int stride = nlogical >> 1; stride >= 1; stride >>= 1) {
-        if (q == 0 && lt >= stride && lt < 2 * stride) sm[lt - stride] = v;
-        __syncthreads();
-        if (lt < stride) v = xyzz_add_q4(v, sm[lt], q);
-        __syncthreads();
-    }
-    return v;
-}
+// same number of logical lanes (512 threads = 128 logical lanes, so that a thread may keep up to 256 VGPRs); block_reduce_q4: curve_quad.hip.h
 constexpr int Q_LOGICAL = 128, Q_THREADS = 4 * Q_LOGICAL;
 
 template <int C> __global__ void __launch_bounds__(Q_THREADS)

@@ -141,24 +141,6 @@ __device__ __forceinline__ uint32_t wave_agg_add(uint32_t* counter, uint32_t key
     return pos;
 }
 
-// the sum of `v` over the 64 lanes of the wave, in every lane (as cells_verify.hip).  Every lane of the wave must call it.
-__device__ __forceinline__ Xyzz mp_wave_sum(Xyzz v)
-{
-#pragma unroll 1
-    for (int d = 32; d >= 1; d >>= 1) {
-        Xyzz o;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            o.x.v[w] = (uint32_t)__shfl_xor((int)v.x.v[w], d, 64);
-            o.y.v[w] = (uint32_t)__shfl_xor((int)v.y.v[w], d, 64);
-            o.zz.v[w] = (uint32_t)__shfl_xor((int)v.zz.v[w], d, 64);
-            o.zzz.v[w] = (uint32_t)__shfl_xor((int)v.zzz.v[w], d, 64);
-        }
-        v = xyzz_add(v, o);
-    }
-    return v;
-}
-
 // Term t < T of the chunk: entries[(2 w + half) T + t] = key | sign, and the histogram of the keys.  One thread per term.
 __global__ void __launch_bounds__(256) k_mp_recode(const Affine* __restrict__ points, const Fr* __restrict__ scalars, size_t T, int c, int windows,
                                                    uint32_t* __restrict__ entries, uint32_t* counts)
@@ -285,7 +267,7 @@ __global__ void __launch_bounds__(64) k_mp_accumulate(const Affine* __restrict__
         Xyzz acc = xyzz_inf();
 #pragma unroll 1
         for (uint32_t e = beg + (LANE ? 0u : threadIdx.x); e < end; e += LANE ? 1u : 64u) acc = xyzz_madd(acc, mp_entry_point(points, sorted[e]));
-        if (!LANE && end - beg > 1) acc = mp_wave_sum(acc);
+        if (!LANE && end - beg > 1) acc = xyzz_wave_sum(acc);
         if (LANE || threadIdx.x == 0) {
             if (of_bucket == 1) xyzz_store(bucket_sums + b, xyzz_add(xyzz_load(bucket_sums + b), acc));
             else xyzz_store(partial + s, acc);
@@ -303,7 +285,7 @@ __global__ void __launch_bounds__(64) k_mp_merge(const uint32_t* __restrict__ se
         Xyzz acc = xyzz_inf();
 #pragma unroll 1
         for (uint32_t s = first + threadIdx.x; s < last; s += 64) acc = xyzz_add(acc, xyzz_load(partial + s));
-        acc = mp_wave_sum(acc);
+        acc = xyzz_wave_sum(acc);
         if (threadIdx.x == 0) xyzz_store(bucket_sums + b, xyzz_add(xyzz_load(bucket_sums + b), acc));
     }
 }
@@ -344,8 +326,8 @@ __global__ void __launch_bounds__(64) k_mp_reduce2(const Xyzz* __restrict__ sg, 
             tt = xyzz_add(tt, xyzz_load(Tg + g0 + g));
         }
     }
-    tt = mp_wave_sum(tt);
-    Xyzz acc = mp_wave_sum(t);
+    tt = xyzz_wave_sum(tt);
+    Xyzz acc = xyzz_wave_sum(t);
 #pragma unroll 1
     for (int d = 1; d < 64; d <<= 1) { // s becomes the suffix sum
         Xyzz o;
@@ -360,7 +342,7 @@ __global__ void __launch_bounds__(64) k_mp_reduce2(const Xyzz* __restrict__ sg, 
         s = xyzz_add(s, o);
     }
     if (lane == 0) s = xyzz_inf();
-    s = mp_wave_sum(s); // sum_l l s_l
+    s = xyzz_wave_sum(s); // sum_l l s_l
 #pragma unroll 1
     for (int i = 0; i < m_log; i++) s = xyzz_dbl(s);
     acc = xyzz_add(acc, s); // sum_g g S_g
@@ -399,12 +381,6 @@ int msm_points_plan(size_t n, int window_bits, int* c, int* windows, size_t* chu
     return BBG_OK;
 }
 
-static bool mp_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *x = (const char*)a, *y = (const char*)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 // d_out = sum_i d_scalars[i] d_points[i] on `st`: 64 B canonical affine, aff_inf() for infinity (n = 0 included).  Queues only.
 int msm_points_run(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size_t n, int window_bits, void* d_out, hipStream_t st)
 {
@@ -412,7 +388,7 @@ int msm_points_run(bbg_ctx* ctx, const void* d_points, const void* d_scalars, si
     MpPlan p;
     if (!mp_plan(n, window_bits, &p)) { set_error(std::string(who) + ": window_bits must be 0 or 2 .. 16 and n at most 2^28"); return BBG_E_INVALID; }
     if (!d_out || (n && (!d_points || !d_scalars))) { set_error(std::string(who) + ": null argument"); return BBG_E_INVALID; }
-    if (n && (mp_overlap(d_out, 64, d_points, n * 64) || mp_overlap(d_out, 64, d_scalars, n * 32))) {
+    if (n && (ranges_overlap(d_out, 64, d_points, n * 64) || ranges_overlap(d_out, 64, d_scalars, n * 32))) {
         set_error(std::string(who) + ": the output overlaps an input");
         return BBG_E_INVALID;
     }

@@ -198,12 +198,6 @@ __global__ void __launch_bounds__(64) k_g2_lines(const G2Aff* __restrict__ point
 }
 
 // ---------------------------------------------------------------------------------------------- the pairing product
-__device__ __forceinline__ bool g1_on_curve(const Affine& a)
-{
-    const Fq one = Fq::one(), three = fe_add(fe_add(one, one), one);
-    return fe_eq(fe_sqr(a.y), fe_add(fe_mul(fe_sqr(a.x), a.x), three));
-}
-
 // Product i < count: slot 0 of the working memory = miller_loop_batch over the finite points among g1[i pairs + j], j < pairs, against
 // lines[j]; flags[i] = 2 where a finite point is off the curve, else 0.  One lane per product; `lines` is read wave-uniformly.
 __global__ void __launch_bounds__(64, 1) k_pair_miller(const char* __restrict__ lines, int pairs, const Affine* __restrict__ g1, size_t count, uint4* __restrict__ work,
@@ -218,7 +212,7 @@ __global__ void __launch_bounds__(64, 1) k_pair_miller(const char* __restrict__ 
         const Affine a = aff_load(mine + j);
         if (!aff_is_inf(a)) {
             live |= 1u << j;
-            if (!g1_on_curve(a)) bad = 2;
+            if (!aff_on_curve(a)) bad = 2;
         }
     }
     Fq12 f = f12_one();
@@ -267,12 +261,6 @@ __global__ void __launch_bounds__(64, 1) k_pair_final(uint4* __restrict__ work, 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static bool pair_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *x = (const char*)a, *y = (const char*)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
-
 // the working memory of a call with `count` products: six lane-interleaved Fq12 slots and one flag word per product of a chunk
 static size_t pair_stride(size_t count) { return (std::min(count, PAIR_CHUNK) + 63) / 64 * 64; }
 static size_t pair_work_bytes(size_t count) { return pair_stride(count) * ((size_t)PairP::FINAL_SLOTS * 384 + 4); }
@@ -392,8 +380,8 @@ int pairing_product_run(bbg_ctx* ctx, const bbg_g2_lines* h, const void* d_g1, s
     const char* who = "bbg_pairing_product_device";
     if (int rc = pairing_product_check(who, ctx, h, d_g1, count, d_out, d_status)) return rc;
     const size_t in_bytes = count * h->pairs * 64;
-    if ((d_out && pair_overlap(d_out, count * 384, d_g1, in_bytes)) || (d_status && pair_overlap(d_status, count * 4, d_g1, in_bytes)) ||
-        (d_out && d_status && pair_overlap(d_out, count * 384, d_status, count * 4))) {
+    if ((d_out && ranges_overlap(d_out, count * 384, d_g1, in_bytes)) || (d_status && ranges_overlap(d_status, count * 4, d_g1, in_bytes)) ||
+        (d_out && d_status && ranges_overlap(d_out, count * 384, d_status, count * 4))) {
         set_error(std::string(who) + ": an output overlaps the input or the other output");
         return BBG_E_INVALID;
     }

@@ -544,16 +544,11 @@ int poly_kate_opening(bbg_ctx* ctx, const void* d_src, void* d_dest, size_t n, c
 }
 
 // ---------------------------------------------------------------------------------------------- Lagrange form (kernels: barycentric.hip)
-static bool ranges_overlap(const void* a, const void* b, size_t bytes)
-{
-    const char *x = (const char*)a, *y = (const char*)b;
-    return x < y + bytes && y < x + bytes;
-}
 int poly_batch_invert(bbg_ctx* ctx, const void* d_in, void* d_out, size_t n, hipStream_t st)
 {
     if (!d_in || !d_out) { set_error("bbg_fr_batch_invert_device: null argument"); return BBG_E_INVALID; }
     if (n == 0) return BBG_OK;
-    if (d_in != d_out && ranges_overlap(d_in, d_out, n * 32)) {
+    if (d_in != d_out && ranges_overlap(d_in, n * 32, d_out, n * 32)) {
         set_error("bbg_fr_batch_invert_device: the output overlaps the input without being the same buffer");
         return BBG_E_INVALID;
     }
@@ -619,7 +614,7 @@ int poly_kate_opening_lagrange(bbg_ctx* ctx, const void* d_evals, void* d_dest, 
         set_error("bbg_kate_opening_lagrange_device: bad argument (1 <= log2n <= 28)");
         return BBG_E_INVALID;
     }
-    if (ranges_overlap(d_evals, d_dest, ((size_t)1 << log2n) * 32)) { set_error("bbg_kate_opening_lagrange_device: dest overlaps the values"); return BBG_E_INVALID; }
+    if (ranges_overlap(d_evals, (size_t)32 << log2n, d_dest, (size_t)32 << log2n)) { set_error("bbg_kate_opening_lagrange_device: dest overlaps the values"); return BBG_E_INVALID; }
     void* d_res = nullptr;
     int rc = poly_evaluate_lagrange_async(ctx, &d_evals, nullptr, 1, log2n, z, d_dest, &d_res, st);
     if (rc) return rc;

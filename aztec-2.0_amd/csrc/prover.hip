@@ -250,10 +250,7 @@ int bbg_prover_create_flavour(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, int fl
     const int program_width = flavour == BBG_FLAVOUR_TURBO ? 4 : 3;
     if (log2n < 3 || log2n > 26) { set_error("bbg_prover_create: need 3 <= log2n <= 26 (the quotient lives on the 4n domain)"); return BBG_E_INVALID; }
     const size_t n = (size_t)1 << log2n;
-    if (srs->s.device != ctx->device) {
-        set_error("bbg_prover_create: the SRS lives on another device than the context (register it on this context)");
-        return BBG_E_INVALID;
-    }
+    if (int rc = check_srs_device("bbg_prover_create", srs->s, ctx, " (register it on this context)")) return rc;
     if (srs->s.n < n + (program_width == 3 ? 1 : 0)) {
         set_error("bbg_prover_create: the SRS needs n points (n + 1 for StandardPLONK: t_high has n + 1 coefficients)");
         return BBG_E_INVALID;

@@ -241,6 +241,22 @@ def test_shim_content_hash_host_logic(tmp_path, threads):
     assert outs[0] and outs[0] == outs[1], "the digest depends on the thread count"
 
 
+def test_stage_layout_host_logic(tmp_path):
+    """csrc/stage_layout.h -- the region arithmetic of every host-array entry point (bbg_capi.hip lays its staging buffer out with it) -- is
+    plain host C++: offsets ascending and multiples of 256, regions disjoint and as large as requested, the total the end of the last region,
+    zero-byte regions accepted, and a request or a sum that does not fit size_t reported instead of wrapped.  Built with g++ under the address
+    and undefined-behaviour sanitizers against the header alone (tests/tools/stage_layout_check.cpp has its own main) and run here as a
+    program of its own."""
+    import subprocess
+    exe = str(tmp_path / "stage_layout_check")
+    src = os.path.join(ROOT, "tests", "tools", "stage_layout_check.cpp")
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert r.returncode == 0, r.stdout.decode()
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert r.returncode == 0 and "stage_layout_check PASS" in r.stdout.decode(), r.stdout.decode()
+
+
 def test_small_msm_final_stage_dataflow_model():
     """csrc/msm_tiny.hip k_tiny_final on INTEGERS (any abelian group will do): 64 quads, two buckets per quad, slices summed, pair sums,
     Hillis-Steele suffix scan, contribution 2 (tail + y) + x, tree -- must equal sum_b b * B_b, the bucket-weighted sum the reference takes with
