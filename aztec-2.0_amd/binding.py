@@ -98,6 +98,8 @@ def load_library():
         "bbg_g2_lines_free": (None, [vp]),
         "bbg_pairing_product_device": (cint, [vp, vp, vp, sz, vp, vp]),
         "bbg_pairing_product": (cint, [vp, vp, vp, sz, vp, vp]),
+        "bbg_pairing_product_wave_device": (cint, [vp, vp, vp, sz, vp, vp]),
+        "bbg_pairing_product_wave": (cint, [vp, vp, vp, sz, vp, vp]),
         "bbg_g1_ntt": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_g1_ntt_device": (cint, [vp, vp, ctypes.c_uint, cint, vp]),
         "bbg_open_all_prepare": (cint, [vp, vp, ctypes.c_uint, ctypes.POINTER(vp)]),
@@ -116,6 +118,8 @@ def load_library():
         "bbg_cells_recover": (cint, [vp, vp, sz, vp, ctypes.c_uint, ctypes.c_uint, sz, vp]),
         "bbg_cells_verify_reduce_device": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp]),
         "bbg_cells_verify_reduce": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "bbg_cells_verify_device": (cint, [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "bbg_cells_verify": (cint, [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "bbg_ntt": (cint, [vp, vp, ctypes.c_uint, cint, sz, vp]),
         "bbg_coset_fft_extend": (cint, [vp, vp, ctypes.c_uint, ctypes.c_uint, vp]),
         "bbg_quotient_widget_device": (cint, [vp, cint, vp, ctypes.c_uint, vp, vp, vp]),
@@ -206,10 +210,10 @@ EXPORTED_SYMBOLS = [
     "bbg_open_all_prepare_cells", "bbg_open_all_count",
     "bbg_open_all_batch_reserve", "bbg_open_all_batch_device", "bbg_open_all_batch",
     "bbg_cells_values_device", "bbg_cells_values", "bbg_cells_recover_device", "bbg_cells_recover",
-    "bbg_cells_verify_reduce_device", "bbg_cells_verify_reduce",
+    "bbg_cells_verify_reduce_device", "bbg_cells_verify_reduce", "bbg_cells_verify_device", "bbg_cells_verify",
     "bbg_g1_msm", "bbg_g1_msm_device", "bbg_g1_msm_plan",
     "bbg_g2_mul", "bbg_g2_lines_prepare", "bbg_g2_lines_pairs", "bbg_g2_lines_read", "bbg_g2_lines_free",
-    "bbg_pairing_product_device", "bbg_pairing_product",
+    "bbg_pairing_product_device", "bbg_pairing_product", "bbg_pairing_product_wave_device", "bbg_pairing_product_wave",
 ]
 
 
@@ -577,6 +581,25 @@ class Bbg:
         self._ck(self.lib.bbg_pairing_product_device(self.ctx, lines.handle, ctypes.c_void_p(d_g1_points), count,
                                                      ctypes.c_void_p(d_out_fq12) if d_out_fq12 else None, ctypes.c_void_p(d_status) if d_status else None))
 
+    def pairing_product_wave(self, lines, g1_points, want_values=True):
+        """pairing_product with one wave per product instead of one lane: the same (values, status), bit for bit; the form for a few
+        products, where latency counts (bbg_pairing_product_wave)."""
+        p = _u64(g1_points, 8)
+        count, rest = divmod(p.shape[0], lines.pairs)
+        if rest:
+            raise ValueError(f"expected a multiple of {lines.pairs} points, got {p.shape[0]}")
+        values = np.zeros((count, 48), dtype=np.uint64) if want_values else None
+        status = np.zeros(count, dtype=np.uint32)
+        self._ck(self.lib.bbg_pairing_product_wave(self.ctx, lines.handle, p.ctypes.data, count, None if values is None else values.ctypes.data,
+                                                   status.ctypes.data))
+        return values, status
+
+    def pairing_product_wave_device(self, lines, d_g1_points, count, d_out_fq12=None, d_status=None):
+        """Device pointers as pairing_product_device; asynchronous on the context stream, no working memory
+        (bbg_pairing_product_wave_device)."""
+        self._ck(self.lib.bbg_pairing_product_wave_device(self.ctx, lines.handle, ctypes.c_void_p(d_g1_points), count,
+                                                          ctypes.c_void_p(d_out_fq12) if d_out_fq12 else None, ctypes.c_void_p(d_status) if d_status else None))
+
     def g1_ntt(self, points, inverse=False):
         """The NTT over G1 of (n, 8) affine points, n a power of two >= 2: out[k] = sum_j w^(jk) P_j, or n^-1 sum_j w^(-jk) P_j with
         inverse; canonical affine, infinite outputs in the affine encoding of infinity (bbg_g1_ntt)."""
@@ -668,6 +691,33 @@ class Bbg:
         self._ck(self.lib.bbg_cells_verify_reduce_device(self.ctx, srs.handle, log2n, log2cell, ctypes.c_void_p(d_commitments), ncom, cids.ctypes.data,
                                                          mids.ctypes.data, mids.shape[0], ctypes.c_void_p(d_values), ctypes.c_void_p(d_proofs),
                                                          rho.ctypes.data, ctypes.c_void_p(d_out), ctypes.c_void_p(d_off_curve) if d_off_curve else None))
+
+    def cells_verify(self, srs, lines, log2n, log2cell, commitments, commitment_ids, cell_ids, values, proofs, rho):
+        """The verdict on K cells (arguments as cells_verify_reduce) against `lines`, the G2Lines of ([x^l]_2, [1]_2): 1 = every proof is
+        valid under rho, 0 = not.  A point off the curve (status 2) raises BbgError (bbg_cells_verify)."""
+        com, prf, v = _u64(commitments, 8), _u64(proofs, 8), _u64(values, 4)
+        cids = np.ascontiguousarray(commitment_ids, dtype=np.uint32).reshape(-1)
+        mids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        K = mids.shape[0]
+        if cids.shape[0] != K or prf.shape[0] != K or v.shape[0] != K << log2cell:
+            raise ValueError(f"expected {K} commitment ids and proofs and {K << log2cell} values")
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        status = ctypes.c_uint32(0)
+        self._ck(self.lib.bbg_cells_verify(self.ctx, srs.handle, lines.handle, log2n, log2cell, com.ctypes.data, com.shape[0], cids.ctypes.data, mids.ctypes.data,
+                                           K, v.ctypes.data, prf.ctypes.data, rho.ctypes.data, ctypes.byref(status)))
+        return int(status.value)
+
+    def cells_verify_device(self, srs, lines, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, d_values, d_proofs, rho, d_status):
+        """Device pointers as cells_verify_reduce_device, d_status one uint32 (1 / 0 / 2); the ids and rho on the host; asynchronous on the
+        context stream (bbg_cells_verify_device)."""
+        cids = np.ascontiguousarray(commitment_ids, dtype=np.uint32).reshape(-1)
+        mids = np.ascontiguousarray(cell_ids, dtype=np.uint32).reshape(-1)
+        if cids.shape[0] != mids.shape[0]:
+            raise ValueError("one commitment id and one cell id per cell")
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        self._ck(self.lib.bbg_cells_verify_device(self.ctx, srs.handle, lines.handle, log2n, log2cell, ctypes.c_void_p(d_commitments), ncom, cids.ctypes.data,
+                                                  mids.ctypes.data, mids.shape[0], ctypes.c_void_p(d_values), ctypes.c_void_p(d_proofs), rho.ctypes.data,
+                                                  ctypes.c_void_p(d_status)))
 
     # ---- NTT
     def ntt(self, coeffs, op=FFT, generator_size=0, constant=None):

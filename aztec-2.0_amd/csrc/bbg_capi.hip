@@ -1105,6 +1105,43 @@ int bbg_cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned
     return BBG_OK;
 }
 
+int bbg_cells_verify_device(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                            const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs,
+                            const uint64_t rho[4], void* d_status)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return cells_verify_run(ctx, srs, lines, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, d_status, ctx->stream);
+}
+
+int bbg_cells_verify(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const uint64_t* commitments, size_t ncom,
+                     const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const uint64_t* values, const uint64_t* proofs,
+                     const uint64_t rho[4], uint32_t* status)
+{
+    CHECK_CTX(ctx);
+    if (!lines || !commitments || !values || !proofs || !status) { set_error("bbg_cells_verify: null argument"); return BBG_E_INVALID; }
+    BBG_TRY(cells_verify_check("bbg_cells_verify", ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho)); // before the staging buffer is sized by K
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t com_bytes = ncom * 64, proof_bytes = K * 64, value_bytes = K * ((size_t)32 << log2cell);
+    Staged st(ctx, "bbg_cells_verify");
+    const auto d_com = st.region(com_bytes), d_proofs = st.region(proof_bytes), d_values = st.region(value_bytes), d_status = st.region(4);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_com, commitments, com_bytes));
+    BBG_TRY(st.up(d_proofs, proofs, proof_bytes));
+    BBG_TRY(st.up(d_values, values, value_bytes));
+    BBG_TRY(cells_verify_run(ctx, srs, lines, log2n, log2cell, st[d_com], ncom, commitment_ids, cell_ids, K, st[d_values], st[d_proofs], rho, st[d_status],
+                             ctx->stream));
+    uint32_t word = 0;
+    BBG_TRY(st.down(&word, d_status, 4));
+    BBG_TRY(st.wait());
+    *status = word;
+    if (word == 2) {
+        set_error("bbg_cells_verify: a commitment or a proof is not on the curve");
+        return BBG_E_INVALID;
+    }
+    return BBG_OK;
+}
+
 int bbg_srs_retain(bbg_srs* srs)
 {
     if (!srs) { set_error("bbg_srs_retain: null handle"); return BBG_E_INVALID; }
@@ -1347,17 +1384,20 @@ int bbg_pairing_product_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const vo
     return pairing_product_run(ctx, lines, d_g1_affine, count, d_out_fq12, d_status, ctx->stream);
 }
 
-int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status)
+// the host form of either pairing product: `run` is the module's device call (pairing_product_run: one lane per product; pairing_wave_run: one wave)
+using PairingRun = int (*)(bbg_ctx*, const bbg_g2_lines*, const void*, size_t, void*, void*, hipStream_t);
+static int pairing_product_host(const char* who, PairingRun run, bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12,
+                                uint32_t* status)
 {
     CHECK_CTX(ctx);
-    if (int rc = pairing_product_check("bbg_pairing_product", ctx, lines, g1_affine, count, out_fq12, status)) return rc; // before the staging buffer is sized by count
+    if (int rc = pairing_product_check(who, ctx, lines, g1_affine, count, out_fq12, status)) return rc; // before the staging buffer is sized by count
     std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t in_bytes = count * lines->pairs * 64;
-    Staged st(ctx, "bbg_pairing_product");
+    Staged st(ctx, who);
     const auto d_values = st.region(count, 384), d_points = st.region(in_bytes), d_flags = st.region(count, 4);
     BBG_TRY(st.ensure());
     BBG_TRY(st.up(d_points, g1_affine, in_bytes));
-    BBG_TRY(pairing_product_run(ctx, lines, st[d_points], count, st[d_values], st[d_flags], ctx->stream));
+    BBG_TRY(run(ctx, lines, st[d_points], count, st[d_values], st[d_flags], ctx->stream));
     std::vector<uint32_t> flags(count);
     BBG_TRY(st.down(flags.data(), d_flags, count * 4));
     if (out_fq12) BBG_TRY(st.down(out_fq12, d_values, count * 384));
@@ -1365,10 +1405,27 @@ int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t*
     if (status) memcpy(status, flags.data(), count * 4);
     const size_t off_curve = (size_t)std::count(flags.begin(), flags.end(), 2u);
     if (off_curve) {
-        set_error("bbg_pairing_product: " + std::to_string(off_curve) + " of the products have a G1 point that is not on the curve");
+        set_error(std::string(who) + ": " + std::to_string(off_curve) + " of the products have a G1 point that is not on the curve");
         return BBG_E_INVALID;
     }
     return BBG_OK;
+}
+
+int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status)
+{
+    return pairing_product_host("bbg_pairing_product", pairing_product_run, ctx, lines, g1_affine, count, out_fq12, status);
+}
+
+int bbg_pairing_product_wave_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d_g1_affine, size_t count, void* d_out_fq12, void* d_status)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return pairing_wave_run(ctx, lines, d_g1_affine, count, d_out_fq12, d_status, ctx->stream);
+}
+
+int bbg_pairing_product_wave(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status)
+{
+    return pairing_product_host("bbg_pairing_product_wave", pairing_wave_run, ctx, lines, g1_affine, count, out_fq12, status);
 }
 
 // ------------------------------------------------------------------------------------------------ NTT

@@ -220,6 +220,9 @@ struct bbg_ctx {
     bbg::DevBuf msm_points_work;
     // pairing.hip: the working set of one bbg_pairing_product call: six lane-interleaved Fq12 slots and a flag word for at most 2^16 products
     bbg::DevBuf pairing_work;
+    // cells_verify.hip: the intermediates of one bbg_cells_verify call (L, R, the packed pair [L, -R], the off-curve count, the pairing's status
+    // word): 512 bytes, sized once
+    bbg::DevBuf cells_verdict;
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
 };
 
@@ -227,7 +230,7 @@ struct bbg_ctx {
 constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::ntt_scratch, &bbg_ctx::staging,  &bbg_ctx::poly_scratch, &bbg_ctx::gp_totals,  &bbg_ctx::quot_setup,
     &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,   &bbg_ctx::cells_work, &bbg_ctx::msm_points_work,
-    &bbg_ctx::pairing_work,
+    &bbg_ctx::pairing_work, &bbg_ctx::cells_verdict,
 };
 
 // bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle.
@@ -405,6 +408,8 @@ int pairing_product_check(const char* who, const bbg_ctx* ctx, const struct bbg_
 // d_out_fq12[i] (may be null) = prod_j e(d_g1[i pairs + j], Q_j), canonical; d_status[i] (may be null) = 1: the product is one, 0: it is not, 2: a
 // finite point of product i is off the curve.  Queues only once ctx->pairing_work has its size.
 int pairing_product_run(bbg_ctx* ctx, const struct bbg_g2_lines* h, const void* d_g1, size_t count, void* d_out_fq12, void* d_status, hipStream_t stream);
+// pairing_wave.hip: the same contract with one WAVE per product (k_pair_wave) and no working memory: queues only, always
+int pairing_wave_run(bbg_ctx* ctx, const struct bbg_g2_lines* h, const void* d_g1, size_t count, void* d_out_fq12, void* d_status, hipStream_t stream);
 // open_all.hip
 int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out);
 int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
@@ -437,4 +442,10 @@ int cells_verify_check(const char* who, const bbg_ctx* ctx, const bbg_srs* srs, 
 int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom, const uint32_t* commitment_ids,
                         const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho, void* d_out, void* d_off_curve,
                         hipStream_t stream);
+// *d_status (uint32) = 1: every proof is valid under rho, 0: not, 2: a finite commitment or proof is off the curve.  `lines`: the handle of
+// ([x^l]_2, [1]_2).  cells_verify_reduce into ctx->cells_verdict, [L, -R] packed there, the wave pairing at count 1, the status word.
+// Queues only once the reduction's working memory has its size.
+int cells_verify_run(bbg_ctx* ctx, bbg_srs* srs, const struct bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                     const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho,
+                     void* d_status, hipStream_t stream);
 } // namespace bbg

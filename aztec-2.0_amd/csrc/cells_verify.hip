@@ -1,4 +1,5 @@
-// A batch of cell proofs reduced to the two points of one pairing check (bbg_cells_verify_reduce).
+// A batch of cell proofs reduced to the two points of one pairing check (bbg_cells_verify_reduce), and at the end of the file
+// the verdict in one call (bbg_cells_verify): that reduction, [L, -R] packed, the wave pairing at count 1, one status word.
 // Notation as in cells.hip: n = 2^log2n, l = 2^log2cell, r = n / l, w = w_n, phi = w^l; cell m < r is { w^(m + r t) : t < l } with the
 // vanishing polynomial X^l - phi^m.  Cell k < K of the batch has a commitment index c_k < ncom, a cell index m_k < r, l values v_k[t], a
 // proof pi_k; I_k is the interpolant of degree < l through its values, rho the caller's challenge, s_b the first l points of a string.
@@ -296,6 +297,54 @@ int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log
         hipLaunchKernelGGL(k_cv_reduce, dim3(np, 2), dim3(64), 0, st, (const Xyzz*)S, r, (const Xyzz*)Q, r + ncom, parts);
         hipLaunchKernelGGL(k_cv_finish, dim3(1), dim3(64), 0, st, (const Xyzz*)parts, np, (const Jacobian*)msm_a, (Affine*)d_out, (const unsigned*)bad,
                            (unsigned*)d_off_curve);
+    }
+    BBG_HIP(hipGetLastError());
+    return BBG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the verdict in one call (bbg_cells_verify)
+// pair[0] = L, pair[1] = -R of lr = (L, R), canonical in and out: y -> p - y; infinity stays as it is, and so does y = 0.  One thread.
+__global__ void __launch_bounds__(64) k_cv_pack(const Affine* __restrict__ lr, Affine* __restrict__ pair)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Affine r = aff_load(lr + 1);
+    if (!aff_is_inf(r)) r.y = fe_reduce_once(fe_reduce_once(fe_neg(r.y))); // 2p - y: p - y behind one subtraction, 0 behind two
+    aff_store(pair, aff_load(lr));
+    aff_store(pair + 1, r);
+}
+// the status word: 2 where the reduction counted a point off the curve, whatever the pairing says; else the pairing's
+__global__ void __launch_bounds__(64) k_cv_verdict(const unsigned* __restrict__ off_curve, const uint32_t* __restrict__ paired, uint32_t* __restrict__ status)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *status = *off_curve ? 2u : *paired;
+}
+
+// the layout of ctx->cells_verdict
+constexpr size_t CVV_LR = 0, CVV_PAIR = 128, CVV_OFF = 256, CVV_PAIRED = 260, CVV_BYTES = 512;
+
+int cells_verify_run(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                     const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho,
+                     void* d_status, hipStream_t st)
+{
+    const std::string who("bbg_cells_verify_device");
+    if (!lines || !d_status || !d_commitments || !d_values || !d_proofs) { set_error(who + ": null argument"); return BBG_E_INVALID; }
+    if (lines->pairs != 2) { set_error(who + ": the lines handle must hold exactly two points, [x^l]_2 and [1]_2"); return BBG_E_INVALID; }
+    if (lines->device != ctx->device) { set_error(who + ": the handle was made on another device"); return BBG_E_INVALID; }
+    if (int rc = cells_verify_check(who.c_str(), ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho)) return rc;
+    const struct { const void* p; size_t bytes; } ins[3] = { { d_commitments, ncom * 64 }, { d_values, (K * 32) << log2cell }, { d_proofs, K * 64 } };
+    for (const auto& in : ins)
+        if (ranges_overlap(d_status, 4, in.p, in.bytes)) { set_error(who + ": the status word overlaps an input"); return BBG_E_INVALID; }
+    if (int rc = ctx->cells_verdict.ensure(CVV_BYTES)) return rc;
+    char* v = (char*)ctx->cells_verdict.p;
+    if (int rc = cells_verify_reduce(ctx, srs, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, v + CVV_LR, v + CVV_OFF, st))
+        return rc;
+    {
+        ProfScope ps(ctx, "cells_verify_pack", st);
+        hipLaunchKernelGGL(k_cv_pack, dim3(1), dim3(64), 0, st, (const Affine*)(v + CVV_LR), (Affine*)(v + CVV_PAIR));
+    }
+    if (int rc = pairing_wave_run(ctx, lines, v + CVV_PAIR, 1, nullptr, v + CVV_PAIRED, st)) return rc;
+    {
+        ProfScope ps(ctx, "cells_verify_pack", st);
+        hipLaunchKernelGGL(k_cv_verdict, dim3(1), dim3(64), 0, st, (const unsigned*)(v + CVV_OFF), (const uint32_t*)(v + CVV_PAIRED), (uint32_t*)d_status);
     }
     BBG_HIP(hipGetLastError());
     return BBG_OK;

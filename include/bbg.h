@@ -261,6 +261,23 @@ int bbg_pairing_product_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const vo
  * anywhere returns BBG_E_INVALID after both outputs have been written, so the caller can see which product it was; every other error
  * leaves them untouched. */
 int bbg_pairing_product(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status);
+/* The wave-cooperative form (csrc/pairing_wave.hip, csrc/fq12_wave.hip.h): exactly the contract of bbg_pairing_product_device -- the same
+ * arguments, layouts, status words 1 / 0 / 2, infinity accepted as data, an all-infinite product is one, the same refusals and the same
+ * count limit 1 .. 2^24 -- with ONE WAVE per product instead of one lane.  Every output is canonical, so the results are bit for bit those
+ * of the lane form, whatever formulas run inside.  One launch (grid = count blocks of 64 threads) does the Miller loop and the final
+ * exponentiation; the Fq12 lives in LDS in the w-basis, a product is 36 Fq2 products on 36 lanes, a sparse product 18, and no Fq12
+ * operation but the one inversion has more than four dependent Fq products on its critical path.  It takes NO working memory: nothing is
+ * grown, ctx's pairing buffer is not touched, and the call never synchronises the host.  Timed under "pairing_wave" (bbg_profile_get).
+ *   Which form to call (profiles/pairing_wave.txt, one MI355X, pairs = 2): the wave form is the latency form, the lane form the
+ * throughput form.  One check takes 1.85 ms here against 17.5 ms there (every wave sample below every lane sample); 1 024 checks 2.04
+ * against 15.1 ms (one wave on every SIMD of the chip: the time is flat up to there), 4 096 checks 7.5 against 15.1 ms, and from 16 384
+ * (28.7 against 15.2 ms; 2^16: 113 against 17.1 ms) the lane form is ahead, because the wave form spends about six times the instructions
+ * per check and the lane form only fills the chip at 2^16.  4 096 is the largest measured count at which the wave form's median is
+ * ahead, at four pairs as well (9.97 against 20.6 ms): call the wave form up to about 4 096 products and the lane form above.
+ * Neither entry point dispatches to the other. */
+int bbg_pairing_product_wave_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d_g1_affine, size_t count, void* d_out_fq12, void* d_status);
+/* The same on HOST arrays, as bbg_pairing_product: synchronous, a status 2 anywhere returns BBG_E_INVALID after both outputs are written. */
+int bbg_pairing_product_wave(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* g1_affine, size_t count, uint64_t* out_fq12, uint32_t* status);
 
 /* The NTT over G1 on plain arrays of points (no counterpart in the reference beyond the recursion inside transform_srs): with n = 2^log2n,
  * 1 <= log2n <= 28, and w_n = fr::get_root_of_unity(log2n), natural order in and out,
@@ -396,6 +413,29 @@ int bbg_cells_verify_reduce_device(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, u
 int bbg_cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, const uint64_t* commitments, size_t ncom,
                             const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const uint64_t* values, const uint64_t* proofs,
                             const uint64_t rho[4], uint64_t out[16]);
+/* The verdict in one call: the reduction above, then e(L, [x^l]_2) e(-R, [1]_2) = 1, with no host round trip in between.  `lines` is a
+ * bbg_g2_lines handle of exactly two points, ([x^l]_2, [1]_2) in that order (bbg_g2_mul makes [x^l]_2); every other argument is
+ * bbg_cells_verify_reduce_device's.  *d_status (one uint32 on the device) becomes
+ *     1   every proof is valid under this rho
+ *     0   not
+ *     2   the reduction counted a finite commitment or proof off the curve, whatever the pairing then says.
+ * The call queues four steps on the context stream -- the reduction, a pack kernel that writes [L, -R] (the negation canonical: p - y;
+ * infinity stays as it is and so does y = 0), bbg_pairing_product_wave_device at count 1, the status word -- and does not synchronise the
+ * host once the reduction's working memory has its size.  L, R, the packed pair, the off-curve count and the pairing's own status word
+ * live in 512 bytes of the context (`scratch` in bbg_memory_report, released by bbg_memory_trim), which every call on the context shares:
+ * calls are ordered on the context stream, each writes its verdict to its OWN d_status as its last step, and so any number of calls may be
+ * queued back to back and read after one synchronisation.
+ *   BBG_E_INVALID with nothing queued and *d_status untouched: a null pointer, a handle with another pair count than two or made on
+ * another device, a status word that overlaps an input, and every refusal of bbg_cells_verify_reduce_device.  Timed under the
+ * reduction's names, "cells_verify_pack" (the pack kernel and the status word) and "pairing_wave". */
+int bbg_cells_verify_device(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                            const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs,
+                            const uint64_t rho[4], void* d_status);
+/* Host-buffer form: upload, the device form, download; synchronous.  Status 2 returns BBG_E_INVALID with *status written; every other
+ * error leaves it untouched. */
+int bbg_cells_verify(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const uint64_t* commitments, size_t ncom,
+                     const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const uint64_t* values, const uint64_t* proofs,
+                     const uint64_t rho[4], uint32_t* status);
 /* The handle's device memory: its own buffers plus the batch workspace it holds at the moment (none before the first reservation or
  * batched call, and none after bbg_open_all_batch_reserve(h, 0)). */
 int bbg_open_all_device_bytes(const struct bbg_open_all* h, size_t* bytes);
@@ -663,7 +703,8 @@ typedef struct bbg_memory_info {
     size_t msm_arena;      /* the MSM scratch arena (entries, sorted values, per-slot bucket sets) */
     size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
                               variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover,
-                              the working set of bbg_cells_verify_reduce, the working memory of bbg_g1_msm and of bbg_pairing_product */
+                              the working set of bbg_cells_verify_reduce, the working memory of bbg_g1_msm and of bbg_pairing_product,
+                              the 512 bytes of bbg_cells_verify */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
