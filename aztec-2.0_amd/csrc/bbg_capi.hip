@@ -917,7 +917,7 @@ int bbg_open_all_prepare(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, struct bbg_
     if (int rc = check_srs_holds("bbg_open_all_prepare", srs->s, log2n)) return rc;
     if (int rc = check_srs_device("bbg_open_all_prepare", srs->s, ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return open_all_prepare(ctx, srs->s.points, log2n, out);
+    return open_all_prepare(ctx, "bbg_open_all_prepare", srs->s.points, log2n, 0, out);
 }
 
 int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log2cell, struct bbg_open_all** out)
@@ -930,7 +930,7 @@ int bbg_open_all_prepare_cells(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsig
     if (int rc = check_srs_holds("bbg_open_all_prepare_cells", srs->s, log2n)) return rc;
     if (int rc = check_srs_device("bbg_open_all_prepare_cells", srs->s, ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return open_cells_prepare(ctx, srs->s.points, log2n, log2cell, out);
+    return open_all_prepare(ctx, "bbg_open_all_prepare_cells", srs->s.points, log2n, log2cell, out);
 }
 
 int bbg_open_all_count(const struct bbg_open_all* h, size_t* proofs)

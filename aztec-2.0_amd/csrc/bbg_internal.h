@@ -233,19 +233,16 @@ constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::pairing_work, &bbg_ctx::cells_verdict,
 };
 
-// bbg_open_all_prepare (open_all.hip): NTT_G1,2n of the reversed SRS prefix and the working arrays of one call, all owned by the handle.
-// bbg_open_all_prepare_cells with l = 2^log2cell > 1, r = n / l: s_hat holds the l transforms at 2r of the string's residue classes
+// bbg_open_all_prepare[_cells] (open_all.hip), l = 2^log2cell, r = n / l: the l transforms at 2r of the string's residue classes (l = 1:
+// NTT_G1,2n of the reversed SRS prefix) and the working arrays of the calls, all owned by the handle.  A workspace is work2 | work1 | sum |
+// c_hat for some number of polynomials, every array polynomial-major, in ONE allocation (open_all_work lays it out).
 struct bbg_open_all {
     bbg_ctx* ctx = nullptr;
     unsigned log2n = 0;
     unsigned log2cell = 0;
     void* s_hat = nullptr;  // 2n x 64 B affine, infinities possible
-    void* work2 = nullptr;  // 2n x 128 B XYZZ: the inverse transform's working array; cells: the 2n products
-    void* work1 = nullptr;  // n x 128 B XYZZ: the forward transform's; cells: r x 128 B
-    void* c_hat = nullptr;  // 2n x 32 B Fr
-    void* sum = nullptr;    // cells only: 2r x 128 B XYZZ, the summed products = the inverse transform's working array
-    // the batched calls' workspace (bbg_open_all_batch_reserve): batch_cap copies of work2 | work1 | sum | c_hat in ONE allocation, every
-    // array polynomial-major.  Owned by the handle like the buffers above, none of which a batched call touches.
+    void* own_ws = nullptr; // the single calls' workspace: one polynomial
+    // the batched calls' workspace (bbg_open_all_batch_reserve): batch_cap polynomials.  A batched call touches nothing of own_ws.
     void* batch_ws = nullptr;
     size_t batch_cap = 0;
     bool batch_lds_attr = false; // the LDS transform's dynamic-LDS limit is raised on this handle's device (hipFuncSetAttribute is per device)
@@ -410,9 +407,8 @@ int pairing_product_check(const char* who, const bbg_ctx* ctx, const struct bbg_
 int pairing_product_run(bbg_ctx* ctx, const struct bbg_g2_lines* h, const void* d_g1, size_t count, void* d_out_fq12, void* d_status, hipStream_t stream);
 // pairing_wave.hip: the same contract with one WAVE per product (k_pair_wave) and no working memory: queues only, always
 int pairing_wave_run(bbg_ctx* ctx, const struct bbg_g2_lines* h, const void* d_g1, size_t count, void* d_out_fq12, void* d_status, hipStream_t stream);
-// open_all.hip
-int open_all_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, struct bbg_open_all** out);
-int open_cells_prepare(bbg_ctx* ctx, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
+// open_all.hip: the handle for 0 <= log2cell <= log2n - 1 (`who`: the entry point, for the text of a HIP error) and a single call
+int open_all_prepare(bbg_ctx* ctx, const char* who, const void* d_srs_points, unsigned log2n, unsigned log2cell, struct bbg_open_all** out);
 int open_all_run(struct bbg_open_all* h, const void* d_coeffs, void* d_out, hipStream_t stream);
 size_t open_all_bytes(unsigned log2n, unsigned log2cell);
 // the batched calls: the workspace of one polynomial, the polynomials one workspace may hold (OPEN_BATCH_BUDGET), the

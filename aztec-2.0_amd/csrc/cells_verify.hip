@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(256) k_cv_scale(Fr* a, size_t l, unsigned log2
 
 // ---------------------------------------------------------------------------------------------- G1 side
 // Item i < K: prod[i] = pw[k] proofs[k], k = perm[i] (group order); item K + c: com_out[c] = W[c] commitments[c].  A finite point off the
-// curve is counted in *bad and taken as infinity.  The shape of k_open_all_pointwise: blocks of one wave, two waves per SIMD, lane tables.
+// curve is counted in *bad and taken as infinity.  The shape of k_open_batch_pointwise: blocks of one wave, two waves per SIMD, lane tables.
 __global__ void __launch_bounds__(64, 2) k_cv_mul(const Affine* __restrict__ proofs, const Fr* __restrict__ pw, const uint32_t* __restrict__ perm, size_t K,
                                                   const Affine* __restrict__ commitments, const Fr* __restrict__ W, size_t ncom, Xyzz* __restrict__ prod,
                                                   Xyzz* __restrict__ com_out, unsigned* bad, Xyzz* __restrict__ tables)

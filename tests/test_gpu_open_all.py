@@ -11,7 +11,7 @@ The SRS is freed between prepare and the first call in every test: the handle ke
 Designed inputs (sections 8 - 11, tests/tools/g1_design.py; tests/test_g1_design_cpu.py holds the designs to their claims).  Over a hashed or
 a random powers string no entry of s_hat = NTT_G1,2n(s^) is infinite and no entry of c_hat = NTT_Fr,2n(c^) is zero, so these cases build
 strings [a_j] G and coefficients whose transforms vanish at chosen indices, and want [k_m] G for the integers k_m = sum_j q^(m)_j a_j:
-  8   infinite entries of the prepared string: k_open_all_pointwise's aff_is_inf branch, k_ecntt_normalize<true>'s stored infinity, and
+  8   infinite entries of the prepared string: k_open_batch_pointwise's aff_is_inf branch, k_ecntt_normalize<true>'s stored infinity, and
       xyzz_mul_glv returning early in some lanes of a wave -- both ends, a wave border, a later round of the lane-stride loop;
   9   zero entries of c_hat: the k = 0 path of xyzz_mul_glv among ordinary products, beside a finite and at an infinite s_hat entry;
   10  powers strings of x = 1, -1, w_n, w_n^3, w_n^-1, w_2n with f = 1 + X + .., 1 - X + .., random: equal and opposite points meet inside

@@ -97,6 +97,20 @@ def test_log2cell_zero_is_the_all_points_opening(oracle, lg):
     assert oc.cell_closed_form_scalars(f, X_INT, 0) == oa.closed_form_scalars(f, X_INT, w)
 
 
+@pytest.mark.parametrize("lg", [1, 2, 3, 4, 5, 6])
+def test_cell_layouts_at_log2cell_zero_are_the_all_points_ones(lg):
+    """The string layout and the coefficient scatter of the cell handle at l = 1 are s^ and c^ of the all-points construction: the one
+    layout kernel and the one scatter kernel of csrc/open_all.hip serve both kinds of handle on this identity."""
+    n = 1 << lg
+    assert oc.string_layout(n, 0) == [n - 2 - i for i in range(n - 1)] + [None] * (n + 1)
+    f = coefficients(SEED + 110 + lg, n)
+    tagged = np.zeros((n, 8), dtype=np.uint64)  # point j carries its index, so that s^ can be read back as indices
+    tagged[:, 0] = np.arange(n)
+    s_hat, c_hat = oa.embedding(tagged, f)
+    assert oc.class_embedding(f, 0, 0) == c_hat
+    assert [None if oa.is_infinity(p) else int(p[0]) for p in s_hat] == oc.string_layout(n, 0)
+
+
 def signs(kind, l, seed):
     rng = np.random.default_rng(seed)
     if kind == "plus":

@@ -103,7 +103,7 @@ def open_cells_embedding(oracle, pts, f, log2cell):
     for b in range(l):
         for i in range(2 * r):
             j = b * 2 * r + i
-            dst = bit_reverse(j, lg + 1)  # k_open_all_pointwise with log2m = log2(2n)
+            dst = bit_reverse(j, lg + 1)  # k_open_batch_pointwise with log2m = log2(2n)
             assert dst == bit_reverse(i, lg2r) * l + bit_reverse(b, log2cell)
             work2[dst] = oracle.g1_mul(s_hat[j], lm.ints_to_mont(oracle, [c_hat[j]])[0])
     work2 = oa.canon_points(oracle, np.stack(work2))
