@@ -197,4 +197,35 @@ __device__ __forceinline__ Xyzz block_reduce_q4(Xyzz v, Xyzz* sm, int nlogical)
     return v;
 }
 
+// ---------------------------------------------------------------------------------- the two forms of an EC operation
+// What a kernel body needs to run either with ONE thread per logical lane (curve.hip.h) or with FOUR (the quad operations above): the MSM's
+// accumulate / reduce kernels are templates over one of these and have one body per stage (msm_kernels.hip.h, k_final_sum in msm.hip).
+//   threads            threads per logical lane
+//   shfl               shuffle distance between adjacent logical lanes
+//   lane(t)            logical lane of thread t
+//   stores()           whether this thread writes its logical lane's results
+//   add / madd / dbl   the group operations (all threads of a logical lane pass the same operands and receive the same result)
+//   block_reduce       tree sum over the block's first `nlogical` logical lanes (sm: nlogical / 2 points); result valid in thread 0
+// EcLane is empty and every member inlines away: a body instantiated with it is the one-lane kernel as it would be written by hand.
+struct EcLane {
+    static constexpr int threads = 1, shfl = 1;
+    __device__ __forceinline__ uint32_t lane(uint32_t t) const { return t; }
+    __device__ __forceinline__ bool stores() const { return true; }
+    __device__ __forceinline__ Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add(a, b); }
+    __device__ __forceinline__ Xyzz madd(const Xyzz& a, const Affine& p) const { return xyzz_madd(a, p); }
+    __device__ __forceinline__ Xyzz dbl(const Xyzz& p) const { return xyzz_dbl(p); }
+    __device__ __forceinline__ Xyzz block_reduce(const Xyzz& v, Xyzz* sm, int nlogical) const { return bbg::block_reduce(v, sm, nlogical); }
+};
+struct EcQuad {
+    static constexpr int threads = 4, shfl = 4;
+    const int q; // this thread's place in its quad (block sizes are multiples of four)
+    __device__ __forceinline__ EcQuad() : q(threadIdx.x & 3) {}
+    __device__ __forceinline__ uint32_t lane(uint32_t t) const { return t >> 2; }
+    __device__ __forceinline__ bool stores() const { return q == 0; }
+    __device__ __forceinline__ Xyzz add(const Xyzz& a, const Xyzz& b) const { return xyzz_add_q4(a, b, q); }
+    __device__ __forceinline__ Xyzz madd(const Xyzz& a, const Affine& p) const { return xyzz_madd_q4(a, p, q); }
+    __device__ __forceinline__ Xyzz dbl(const Xyzz& p) const { return xyzz_dbl_q4(p, q); }
+    __device__ __forceinline__ Xyzz block_reduce(const Xyzz& v, Xyzz* sm, int nlogical) const { return block_reduce_q4(v, sm, nlogical); }
+};
+
 } // namespace bbg

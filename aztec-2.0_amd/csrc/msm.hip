@@ -96,31 +96,28 @@ __global__ void __launch_bounds__(128) k_srs_hashed(Affine* out, size_t n, uint6
     for (int e = cnt - 1; e >= 0; e--) aff_batch_finish(out + i0 + e, fin[e], zw[e], prefix[e], inv, aff_inf());
 }
 
-// ---------------------------------------------------------------------------------- last reduce stage, g1 helpers (block_reduce[_q4]: curve_quad.hip.h)
-__global__ void __launch_bounds__(64, 1) k_final_sum(const Xyzz* __restrict__ planes, int nplanes, Jacobian* out)
-{
-    __shared__ Xyzz sm[16];
-    planes += (size_t)blockIdx.x * MSM_MAX_PLANES; // one block per MSM of the batch
-    out += blockIdx.x;
-    Xyzz v = (int)threadIdx.x < nplanes ? xyzz_load(planes + threadIdx.x) : xyzz_inf();
-    v = block_reduce(v, sm, MSM_MAX_PLANES);
-    if (threadIdx.x == 0) {
-        Jacobian j = xyzz_to_jacobian(v);
-        fe_store<FqP>(&out->x, j.x);
-        fe_store<FqP>(&out->y, j.y);
-        fe_store<FqP>(&out->z, j.z);
-    }
-}
-__global__ void __launch_bounds__(4 * MSM_MAX_PLANES) k_final_sum_q(const Xyzz* __restrict__ planes, int nplanes, Jacobian* out)
+// ---------------------------------------------------------------------------------- last reduce stage, g1 helpers (EC forms, block_reduce[_q4]: curve_quad.hip.h)
+// One block per MSM of the batch adds its bit planes, one plane per logical lane.  EcLane: one wave, a tree over all MSM_MAX_PLANES lanes.
+// EcQuad: four threads per plane, and the tree only as wide as the planes need (15 planes -> 4 levels, not 5).
+template <class Form> struct FinalSumBlock {
+    static constexpr int threads = Form::threads == 1 ? 64 : Form::threads * MSM_MAX_PLANES;
+    static constexpr int min_waves = Form::threads == 1 ? 1 : 0; // second argument of __launch_bounds__ (0: none)
+};
+template <class Form> __global__ void __launch_bounds__(FinalSumBlock<Form>::threads, FinalSumBlock<Form>::min_waves)
+k_final_sum(const Xyzz* __restrict__ planes, int nplanes, Jacobian* out)
 {
     __shared__ Xyzz sm[MSM_MAX_PLANES / 2];
-    const int lt = threadIdx.x >> 2;
-    planes += (size_t)blockIdx.x * MSM_MAX_PLANES; // one block per MSM of the batch
+    const Form f{};
+    const int lt = (int)f.lane(threadIdx.x);
+    planes += (size_t)blockIdx.x * MSM_MAX_PLANES;
     out += blockIdx.x;
     Xyzz v = lt < nplanes ? xyzz_load(planes + lt) : xyzz_inf();
-    int width = 1;
-    while (width < nplanes) width <<= 1; // 15 planes -> 4 levels, not 5
-    v = block_reduce_q4(v, sm, width);
+    int width = MSM_MAX_PLANES;
+    if constexpr (Form::threads != 1) {
+        width = 1;
+        while (width < nplanes) width <<= 1;
+    }
+    v = f.block_reduce(v, sm, width);
     if (threadIdx.x == 0) {
         Jacobian j = xyzz_to_jacobian(v);
         fe_store<FqP>(&out->x, j.x);
@@ -130,8 +127,9 @@ __global__ void __launch_bounds__(4 * MSM_MAX_PLANES) k_final_sum_q(const Xyzz* 
 }
 int msm_launch_final_sum(bool quad, const void* d_planes, int nplanes, void* d_out_jac, hipStream_t st, int sets)
 {
-    if (quad) hipLaunchKernelGGL(k_final_sum_q, dim3(sets), dim3(4 * MSM_MAX_PLANES), 0, st, (const Xyzz*)d_planes, nplanes, (Jacobian*)d_out_jac);
-    else hipLaunchKernelGGL(k_final_sum, dim3(sets), dim3(64), 0, st, (const Xyzz*)d_planes, nplanes, (Jacobian*)d_out_jac);
+    const auto kernel = quad ? k_final_sum<EcQuad> : k_final_sum<EcLane>;
+    const int block = quad ? FinalSumBlock<EcQuad>::threads : FinalSumBlock<EcLane>::threads;
+    hipLaunchKernelGGL(kernel, dim3(sets), dim3(block), 0, st, (const Xyzz*)d_planes, nplanes, (Jacobian*)d_out_jac);
     BBG_HIP(hipGetLastError());
     return BBG_OK;
 }

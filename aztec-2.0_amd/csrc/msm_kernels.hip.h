@@ -515,7 +515,7 @@ template <int C> __global__ void k_offsets(const uint32_t* __restrict__ keys, si
 // and k_combine adds head/tail pieces per bucket.  Values address the window tables: point = table[w*n_srs + idx],
 // negated when bit 31 is set.
 constexpr uint32_t MSM_SEG_MIN = 8, MSM_SEG_DEFAULT = 64; // segment length is chosen per call (msm_seg_len)
-constexpr size_t MSM_QUAD_ACC_MAX_LANES = 32768; // k_accumulate_q4 up to this many lane segments (two waves per SIMD of quads)
+constexpr size_t MSM_QUAD_ACC_MAX_LANES = 32768; // the four-thread k_accumulate up to this many lane segments (two waves per SIMD of quads)
 constexpr int MSM_LONG_SPAN = 48; // buckets spanning more lanes than this are summed by a whole block
 
 template <int C> __device__ __forceinline__ Affine load_entry_point(const Affine* __restrict__ table, size_t n_srs, uint32_t v)
@@ -524,16 +524,20 @@ template <int C> __device__ __forceinline__ Affine load_entry_point(const Affine
     return aff_load(table + (size_t)((v >> K::idx_bits) & ((1u << K::win_bits) - 1)) * n_srs + (v & ((1u << K::idx_bits) - 1)));
 }
 
-template <int C> __global__ void __launch_bounds__(256)
+// Form = EcLane: one thread per lane segment.  Form = EcQuad: FOUR threads per segment share every mixed addition -- identical control flow
+// and results, the chain of dependent additions ~2x shorter in time.  Only for small MSMs (few lanes: the chip is idle anyway and the
+// kernel's run time is that chain); a quad-cooperative addition costs ~1.5x the instructions of a one-lane one.
+template <int C, class Form> __global__ void __launch_bounds__(256)
 k_accumulate(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ offsets, const Affine* __restrict__ table,
              size_t n_srs, uint32_t seg, Xyzz* head, Xyzz* tail, Xyzz* buckets, uint32_t nb)
 {
+    const Form f{};
     const uint32_t MSM_BUCKETS = nb; // sets x 2^(C-1): every MSM of the batch has its own bucket set
     const uint32_t total = offsets[MSM_BUCKETS + 1]; // the partition sort drops zero digits: the count lives on the device
-    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = f.lane(blockIdx.x * blockDim.x + threadIdx.x);
     const uint32_t base = offsets[1]; // entries with key 0 (zero digits) sort first and are skipped
     const uint64_t s64 = (uint64_t)base + (uint64_t)lane * seg;
-    if (s64 >= total) return;
+    if (s64 >= total) return; // the threads of a logical lane leave together
     const uint32_t s = (uint32_t)s64;
     const uint32_t e = (total - s > seg) ? s + seg : total;
     // bucket containing position s: largest b in [1, 2^15] with offsets[b] <= s
@@ -551,8 +555,10 @@ k_accumulate(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ off
     Affine p = load_entry_point<C>(table, n_srs, v);
     for (uint32_t q = s; q < e; q++) {
         if (q == cur_end) { // the run of bucket `cur` ended inside this segment
-            if (first_run) xyzz_store(head + lane, acc);
-            else xyzz_store(buckets + (cur - 1), acc);
+            if (f.stores()) {
+                if (first_run) xyzz_store(head + lane, acc);
+                else xyzz_store(buckets + (cur - 1), acc);
+            }
             first_run = false;
             acc = xyzz_inf();
             do {
@@ -566,62 +572,9 @@ k_accumulate(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ off
             v = vals[q + 1];
             p = load_entry_point<C>(table, n_srs, v);
         }
-        acc = xyzz_madd(acc, aff_neg_if(pc, (vc >> 31) != 0));
+        acc = f.madd(acc, aff_neg_if(pc, (vc >> 31) != 0));
     }
-    if (first_run) xyzz_store(head + lane, acc);
-    else xyzz_store(tail + lane, acc);
-}
-
-// The same accumulation with FOUR threads per lane segment (xyzz_madd_q4): identical control flow and results, the chain of dependent mixed
-// additions ~2x shorter in time.  Only for small MSMs (few lanes: the chip is idle anyway and the kernel's run time is that chain); a
-// quad-cooperative addition costs ~1.5x the instructions of a one-lane one.
-template <int C> __global__ void __launch_bounds__(256)
-k_accumulate_q4(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ offsets, const Affine* __restrict__ table,
-                size_t n_srs, uint32_t seg, Xyzz* head, Xyzz* tail, Xyzz* buckets, uint32_t nb)
-{
-    const uint32_t MSM_BUCKETS = nb; // sets x 2^(C-1): every MSM of the batch has its own bucket set
-    const uint32_t total = offsets[MSM_BUCKETS + 1];
-    const uint32_t lane = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    const int qd = threadIdx.x & 3;
-    const uint32_t base = offsets[1];
-    const uint64_t s64 = (uint64_t)base + (uint64_t)lane * seg;
-    if (s64 >= total) return; // whole quads leave together
-    const uint32_t s = (uint32_t)s64;
-    const uint32_t e = (total - s > seg) ? s + seg : total;
-    uint32_t lo = 1, hi = MSM_BUCKETS;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (offsets[mid] <= s) lo = mid;
-        else hi = mid - 1;
-    }
-    uint32_t cur = lo;
-    uint32_t cur_end = offsets[cur + 1];
-    bool first_run = true;
-    Xyzz acc = xyzz_inf();
-    uint32_t v = vals[s];
-    Affine p = load_entry_point<C>(table, n_srs, v);
-    for (uint32_t q = s; q < e; q++) {
-        if (q == cur_end) {
-            if (qd == 0) {
-                if (first_run) xyzz_store(head + lane, acc);
-                else xyzz_store(buckets + (cur - 1), acc);
-            }
-            first_run = false;
-            acc = xyzz_inf();
-            do {
-                cur++;
-                cur_end = offsets[cur + 1];
-            } while (cur_end <= q);
-        }
-        const uint32_t vc = v;
-        const Affine pc = p;
-        if (q + 1 < e) {
-            v = vals[q + 1];
-            p = load_entry_point<C>(table, n_srs, v);
-        }
-        acc = xyzz_madd_q4(acc, aff_neg_if(pc, (vc >> 31) != 0), qd);
-    }
-    if (qd == 0) {
+    if (f.stores()) {
         if (first_run) xyzz_store(head + lane, acc);
         else xyzz_store(tail + lane, acc);
     }
@@ -811,7 +764,67 @@ k_redo(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ offsets, 
     }
 }
 
-// piece of bucket b held by lane l (see k_accumulate): head if the bucket starts at or before the lane's segment start
+// ---------------------------------------------------------------------------------- reduce phase
+// Every stage either with one thread per EC operation (EcLane) or with four (EcQuad, curve_quad.hip.h: a logical lane = thread / 4; identical
+// structure and results, the dependency chain ~3x shorter in time), chosen per stage by the bits of msm_reduce_quad.  One body per stage, a
+// template over the form.  A block carries 256 logical lanes of one thread, or 128 of four (512 threads, so that a thread may keep up to 256 VGPRs).
+constexpr int Q_LOGICAL = 128, Q_THREADS = 4 * Q_LOGICAL;
+template <class Form> struct ReduceBlock {
+    static constexpr int logical = Form::threads == 1 ? 256 : Q_LOGICAL; // logical lanes per block
+    static constexpr int threads = logical * Form::threads;
+    static constexpr int min_waves = Form::threads == 1 ? 1 : 0; // second argument of __launch_bounds__ (0: none)
+};
+
+// What k_accumulate left of bucket b, and so what a combine kernel has to do for it.  Lanes l0 .. l1 hold its entries; at_start: the bucket
+// starts where lane l0's segment starts, so l0's piece is that lane's head (otherwise its tail).
+enum BucketKind {
+    BUCKET_EMPTY,    // no entries: the bucket is the point at infinity
+    BUCKET_HEAD,     // one lane, from its segment's start: head[l0]
+    BUCKET_TAIL,     // one lane, up to its segment's end: tail[l0]
+    BUCKET_COMPLETE, // strictly inside one segment: k_accumulate stored it already
+    BUCKET_LONG,     // more than MSM_LONG_SPAN lanes: queued for k_combine_long
+    BUCKET_PIECES,   // the pieces of lanes l0 .. l1 have to be added
+};
+struct BucketRun {
+    BucketKind kind;
+    uint32_t l0, l1;
+    bool at_start;
+};
+// the lanes of a bucket that has entries (kind is not set)
+__device__ __forceinline__ BucketRun bucket_lanes(const uint32_t* __restrict__ offsets, uint32_t base, uint32_t seg, uint32_t b)
+{
+    const uint32_t sb = offsets[b], eb = offsets[b + 1];
+    BucketRun r;
+    r.l0 = (sb - base) / seg;
+    r.l1 = (eb - 1 - base) / seg;
+    r.at_start = (sb == base + r.l0 * seg);
+    return r;
+}
+__device__ __forceinline__ BucketRun bucket_classify(const uint32_t* __restrict__ offsets, uint32_t base, uint32_t total, uint32_t seg, uint32_t b)
+{
+    const uint32_t sb = offsets[b], eb = offsets[b + 1];
+    if (sb == eb) return BucketRun{BUCKET_EMPTY, 0, 0, false};
+    BucketRun r = bucket_lanes(offsets, base, seg, b);
+    if (r.l0 == r.l1) {
+        uint32_t seg_end = base + (r.l0 + 1) * seg;
+        if (seg_end > total || seg_end < base) seg_end = total; // the last segment is short; (l0 + 1) * seg may wrap at 2^32
+        if (r.at_start) r.kind = BUCKET_HEAD;
+        else if (eb == seg_end) r.kind = BUCKET_TAIL;
+        else r.kind = BUCKET_COMPLETE;
+    } else if (r.l1 - r.l0 > (uint32_t)MSM_LONG_SPAN) {
+        r.kind = BUCKET_LONG;
+    } else {
+        r.kind = BUCKET_PIECES;
+    }
+    return r;
+}
+__device__ __forceinline__ void long_push(uint32_t* long_count, uint32_t* long_list, uint32_t b)
+{
+    const uint32_t slot = atomicAdd(long_count, 1u);
+    long_list[slot] = b;
+}
+
+// piece of a bucket held by lane l (see k_accumulate): head if the bucket starts at or before the lane's segment start
 __device__ __forceinline__ Xyzz bucket_piece(const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail, uint32_t l, uint32_t l0,
                                              bool starts_at_seg_start)
 {
@@ -819,8 +832,8 @@ __device__ __forceinline__ Xyzz bucket_piece(const Xyzz* __restrict__ head, cons
     return xyzz_load(head + l);
 }
 
-// buckets[b-1] = sum of the pieces of bucket b; complete ("middle") runs were already written by k_accumulate.
-// Buckets spanning more than MSM_LONG_SPAN lanes (skewed scalar distributions) are queued for k_combine_long.
+// buckets[b-1] = sum of the pieces of bucket b, one thread per bucket (the one-lane combine when lanes <= 2 x buckets).
+// Stays a kernel of its own beside k_combine_q: its even / odd bucket order and its per-block compaction are measured choices of the one-lane form.
 template <int C> __global__ void __launch_bounds__(256, 1)
 k_combine(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail,
           Xyzz* buckets, uint32_t* long_count, uint32_t* long_list, uint32_t nb)
@@ -839,37 +852,52 @@ k_combine(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __rest
         constexpr uint32_t PER_SET = MsmCfg<C>::buckets;
         const uint32_t set = t / PER_SET, r = t % PER_SET;
         const uint32_t b = set * PER_SET + (r < PER_SET / 2 ? 2 * (r + 1) : 2 * (r - PER_SET / 2) + 1);
-        const uint32_t sb = offsets[b], eb = offsets[b + 1];
-        if (sb == eb) {
-            xyzz_store(buckets + (b - 1), xyzz_inf());
-        } else {
-            const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-            const bool at_start = (sb == base + l0 * seg);
-            if (l0 == l1) {
-                uint32_t seg_end = base + (l0 + 1) * seg;
-                if (seg_end > total || seg_end < base) seg_end = total;
-                if (at_start) xyzz_store(buckets + (b - 1), xyzz_load(head + l0));
-                else if (eb == seg_end) xyzz_store(buckets + (b - 1), xyzz_load(tail + l0));
-                // else: complete run, already stored
-            } else if (l1 - l0 > (uint32_t)MSM_LONG_SPAN) {
-                const uint32_t slot = atomicAdd(long_count, 1u);
-                long_list[slot] = b;
-            } else {
-                work[atomicAdd(&nwork, 1u)] = b;
-            }
-        }
+        const BucketRun run = bucket_classify(offsets, base, total, seg, b);
+        if (run.kind == BUCKET_EMPTY) xyzz_store(buckets + (b - 1), xyzz_inf());
+        else if (run.kind == BUCKET_HEAD) xyzz_store(buckets + (b - 1), xyzz_load(head + run.l0));
+        else if (run.kind == BUCKET_TAIL) xyzz_store(buckets + (b - 1), xyzz_load(tail + run.l0));
+        else if (run.kind == BUCKET_LONG) long_push(long_count, long_list, b);
+        else if (run.kind == BUCKET_PIECES) work[atomicAdd(&nwork, 1u)] = b;
     }
     __syncthreads();
     // About half of the buckets straddle a segment boundary and need one addition (rarely two): compacted, the additions fill whole waves
     // instead of half of every wave (37 M -> ~20 M VALU instructions per launch at n = 2^20).
     if (threadIdx.x < nwork) {
         const uint32_t b = work[threadIdx.x];
-        const uint32_t sb = offsets[b], eb = offsets[b + 1];
-        const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-        Xyzz acc = bucket_piece(head, tail, l0, l0, sb == base + l0 * seg);
-        for (uint32_t l = l0 + 1; l <= l1; l++) acc = xyzz_add(acc, xyzz_load(head + l));
+        const BucketRun run = bucket_lanes(offsets, base, seg, b);
+        Xyzz acc = bucket_piece(head, tail, run.l0, run.l0, run.at_start);
+        for (uint32_t l = run.l0 + 1; l <= run.l1; l++) acc = xyzz_add(acc, xyzz_load(head + l));
         xyzz_store(buckets + (b - 1), acc);
     }
+}
+
+// The same with four threads per bucket: bucket order as stored, no compaction (a quad's additions wait for nobody else's).
+// Stays apart from k_combine_lanes<C, EcQuad>: one logical lane per bucket needs neither the butterfly nor an accumulator that starts at
+// infinity -- it loads its first piece.
+template <int C> __global__ void __launch_bounds__(Q_THREADS)
+k_combine_q(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail,
+            Xyzz* buckets, uint32_t* long_count, uint32_t* long_list, uint32_t nb)
+{
+    const EcQuad f{};
+    const uint32_t MSM_BUCKETS = nb; // sets x 2^(C-1): every MSM of the batch has its own bucket set
+    const uint32_t total = offsets[MSM_BUCKETS + 1];
+    const uint32_t b = f.lane(blockIdx.x * blockDim.x + threadIdx.x) + 1;
+    if (b > MSM_BUCKETS) return;
+    const uint32_t base = offsets[1];
+    const BucketRun run = bucket_classify(offsets, base, total, seg, b);
+    if (run.kind == BUCKET_COMPLETE) return;
+    if (run.kind == BUCKET_LONG) {
+        if (f.stores()) long_push(long_count, long_list, b);
+        return;
+    }
+    Xyzz acc = xyzz_inf();
+    if (run.kind == BUCKET_HEAD) acc = xyzz_load(head + run.l0);
+    else if (run.kind == BUCKET_TAIL) acc = xyzz_load(tail + run.l0);
+    else if (run.kind == BUCKET_PIECES) {
+        acc = bucket_piece(head, tail, run.l0, run.l0, run.at_start);
+        for (uint32_t l = run.l0 + 1; l <= run.l1; l++) acc = f.add(acc, xyzz_load(head + l));
+    }
+    if (f.stores()) xyzz_store(buckets + (b - 1), acc);
 }
 
 __device__ __forceinline__ Xyzz xyzz_shfl_xor(const Xyzz& v, int mask)
@@ -885,78 +913,69 @@ __device__ __forceinline__ Xyzz xyzz_shfl_xor(const Xyzz& v, int mask)
     return r;
 }
 
-// Latency-oriented variant of k_combine: MSM_COMBINE_LANES adjacent lanes share a bucket, each sums every 4th piece, then
-// a butterfly over the lane group (a bucket of ~512 entries has ~9 pieces: the serial chain drops from 8 additions to
-// 5).  4 lanes, not 8: the butterfly runs in lock-step on every lane, and with 8 the reduce phase (which shares the chip
+// Latency-oriented variant of k_combine (lanes > 2 x buckets: several pieces per bucket): MSM_COMBINE_LANES adjacent logical lanes share a
+// bucket, each sums every 4th piece, then a butterfly over the lane group (a bucket of ~512 entries has ~9 pieces: the serial chain drops
+// from 8 additions to 5).  4 lanes, not 8: the butterfly runs in lock-step on every lane, and with 8 the reduce phase (which shares the chip
 // with the next MSM's accumulation) cost 40 lane-additions per bucket instead of 17 -- 5 % of the pipelined step time.
 constexpr int MSM_COMBINE_LANES = 4;
-template <int C> __global__ void __launch_bounds__(256, 1)
+template <int C, class Form> __global__ void __launch_bounds__(ReduceBlock<Form>::threads, ReduceBlock<Form>::min_waves)
 k_combine_lanes(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail,
-           Xyzz* buckets, uint32_t* long_count, uint32_t* long_list, uint32_t nb)
+                Xyzz* buckets, uint32_t* long_count, uint32_t* long_list, uint32_t nb)
 {
+    const Form f{};
     const uint32_t MSM_BUCKETS = nb; // sets x 2^(C-1): every MSM of the batch has its own bucket set
     const uint32_t total = offsets[MSM_BUCKETS + 1];
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t b = gid / MSM_COMBINE_LANES + 1;
-    const uint32_t r = gid % MSM_COMBINE_LANES;
-    if (b > MSM_BUCKETS) return; // whole lane groups drop out together (grid is a multiple of 8)
+    const uint32_t gl = f.lane(blockIdx.x * blockDim.x + threadIdx.x);
+    const uint32_t b = gl / MSM_COMBINE_LANES + 1;
+    const uint32_t r = gl % MSM_COMBINE_LANES;
+    if (b > MSM_BUCKETS) return; // whole waves drop out together (a wave holds whole lane groups, the grid whole blocks)
     const uint32_t base = offsets[1];
-    const uint32_t sb = offsets[b], eb = offsets[b + 1];
+    const BucketRun run = bucket_classify(offsets, base, total, seg, b);
     bool store = true, reduce = false;
     Xyzz acc = xyzz_inf();
-    if (sb != eb) {
-        const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-        const bool at_start = (sb == base + l0 * seg);
-        if (l0 == l1) {
-            uint32_t seg_end = base + (l0 + 1) * seg;
-            if (seg_end > total || seg_end < base) seg_end = total;
-            if (at_start) acc = xyzz_load(head + l0);
-            else if (eb == seg_end) acc = xyzz_load(tail + l0);
-            else store = false; // complete run, already written by k_accumulate
-        } else if (l1 - l0 > (uint32_t)MSM_LONG_SPAN) {
-            if (r == 0) {
-                const uint32_t slot = atomicAdd(long_count, 1u);
-                long_list[slot] = b;
-            }
-            store = false;
-        } else {
-            reduce = true;
-            for (uint32_t l = l0 + r; l <= l1; l += MSM_COMBINE_LANES) acc = xyzz_add(acc, bucket_piece(head, tail, l, l0, at_start));
-        }
+    if (run.kind == BUCKET_HEAD) acc = xyzz_load(head + run.l0);
+    else if (run.kind == BUCKET_TAIL) acc = xyzz_load(tail + run.l0);
+    else if (run.kind == BUCKET_COMPLETE) store = false;
+    else if (run.kind == BUCKET_LONG) {
+        if (r == 0 && f.stores()) long_push(long_count, long_list, b);
+        store = false;
+    } else if (run.kind == BUCKET_PIECES) {
+        reduce = true;
+        for (uint32_t l = run.l0 + r; l <= run.l1; l += MSM_COMBINE_LANES) acc = f.add(acc, bucket_piece(head, tail, l, run.l0, run.at_start));
     }
     // the butterfly is executed by all lanes of the wave (shuffles need every lane); groups that do not reduce carry infinities
-    if (!reduce && !(sb != eb && store)) acc = xyzz_inf();
     const unsigned long long any = __ballot(reduce);
     if (any) {
         Xyzz part = reduce ? acc : xyzz_inf();
-        for (int m = MSM_COMBINE_LANES >> 1; m >= 1; m >>= 1) part = xyzz_add(part, xyzz_shfl_xor(part, m));
+        for (int m = MSM_COMBINE_LANES >> 1; m >= 1; m >>= 1) part = f.add(part, xyzz_shfl_xor(part, Form::shfl * m));
         if (reduce) acc = part;
     }
-    if (store && r == 0) xyzz_store(buckets + (b - 1), acc);
+    if (store && r == 0 && f.stores()) xyzz_store(buckets + (b - 1), acc);
 }
 
-
 // one block per queued long bucket (grid-stride over the queue)
-template <int C> __global__ void __launch_bounds__(256, 1)
+template <int C, class Form> __global__ void __launch_bounds__(ReduceBlock<Form>::threads, ReduceBlock<Form>::min_waves)
 k_combine_long(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail, Xyzz* buckets,
                const uint32_t* __restrict__ long_count, const uint32_t* __restrict__ long_list)
 {
-    __shared__ Xyzz sm[128];
+    constexpr int LOGICAL = ReduceBlock<Form>::logical;
+    __shared__ Xyzz sm[LOGICAL / 2];
+    const Form f{};
+    const uint32_t lt = f.lane(threadIdx.x);
     const uint32_t cnt = *long_count;
     const uint32_t base = offsets[1];
     for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) {
         const uint32_t b = long_list[i];
-        const uint32_t sb = offsets[b], eb = offsets[b + 1];
-        const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-        const bool at_start = (sb == base + l0 * seg);
+        const BucketRun run = bucket_lanes(offsets, base, seg, b);
         Xyzz acc = xyzz_inf();
-        for (uint32_t l = l0 + threadIdx.x; l <= l1; l += 256) acc = xyzz_add(acc, bucket_piece(head, tail, l, l0, at_start));
-        acc = block_reduce(acc, sm, 256);
+        for (uint32_t l = run.l0 + lt; l <= run.l1; l += LOGICAL) acc = f.add(acc, bucket_piece(head, tail, l, run.l0, run.at_start));
+        acc = f.block_reduce(acc, sm, LOGICAL);
         if (threadIdx.x == 0) xyzz_store(buckets + (b - 1), acc);
         __syncthreads();
     }
 }
 
+// The row / column sums stay two kernels: the four-thread one is another algorithm (a serial share per THREAD, then quad_sum4, then the tree).
 // weight of bucket index idx (0-based) is idx + 1 = hi*COLS + lo + 1  (COLS = 2^log_cols, ROWS = 2^log_rows).
 // blocks 0..ROWS-1: Row_hi = sum_lo B[hi][lo] ; blocks ROWS..ROWS+COLS-1: Col_lo = sum_hi B[hi][lo].
 template <int C> __global__ void __launch_bounds__(256, 1) k_rowcol(const Xyzz* __restrict__ buckets, Xyzz* rows, Xyzz* cols)
@@ -979,143 +998,6 @@ template <int C> __global__ void __launch_bounds__(256, 1) k_rowcol(const Xyzz* 
         for (int hi = tid; hi < ROWS; hi += 256) v = xyzz_add(v, xyzz_load(buckets + (size_t)hi * COLS + lo));
         v = block_reduce(v, sm, 256);
         if (tid == 0) xyzz_store(cols + lo, v);
-    }
-}
-
-// sum_b b*B_b = COLS * sum_hi hi*Row_hi + sum_lo (lo+1)*Col_lo = sum_t 2^t H_t with the bit planes
-//   H_t = sum_{lo : bit t of (lo+1)} Col_lo  +  sum_{hi : bit (t - log_cols) of hi} Row_hi        (t = 0 .. C-2).
-// One block per bit plane: tree-sum the selected rows/columns, then t doublings by one lane -- the planes run side by
-// side, so the serial depth is ~9 additions + t doublings instead of a double-and-add on top of a tree plus log_cols more
-// doublings.  k_final_sum adds the planes and converts to the reference's Jacobian layout.
-template <int C> __global__ void __launch_bounds__(256, 1) k_final_planes(const Xyzz* __restrict__ rows, const Xyzz* __restrict__ cols, Xyzz* planes)
-{
-    constexpr int ROWS = 1 << MsmCfg<C>::log_rows, COLS = 1 << MsmCfg<C>::log_cols, LOGC = MsmCfg<C>::log_cols;
-    __shared__ Xyzz sm[128];
-    const int t = blockIdx.x, tid = threadIdx.x;
-    rows += (size_t)blockIdx.y * ROWS;
-    cols += (size_t)blockIdx.y * COLS;
-    planes += (size_t)blockIdx.y * MSM_MAX_PLANES;
-    Xyzz v = xyzz_inf();
-    if (t <= LOGC)
-        for (int lo = tid; lo < COLS; lo += 256)
-            if (((lo + 1) >> t) & 1) v = xyzz_add(v, xyzz_load(cols + lo));
-    if (t >= LOGC)
-        for (int hi = tid; hi < ROWS; hi += 256)
-            if ((hi >> (t - LOGC)) & 1) v = xyzz_add(v, xyzz_load(rows + hi));
-    v = block_reduce(v, sm, 256);
-    if (tid == 0) {
-        for (int k = 0; k < t; k++) v = xyzz_dbl(v);
-        xyzz_store(planes + t, v);
-    }
-}
-
-// ------------------------------------------------------------------------------------ quad-cooperative reduce phase
-// The same reduce phase with every EC operation shared by FOUR adjacent lanes (curve_quad.hip.h): a logical lane lt = thread / 4,
-// q = thread % 4.  Identical structure and results; the dependency chain is ~3x shorter in time.  Blocks carry 4x the threads for the
-// same number of logical lanes (512 threads = 128 logical lanes, so that a thread may keep up to 256 VGPRs); block_reduce_q4: curve_quad.hip.h
-constexpr int Q_LOGICAL = 128, Q_THREADS = 4 * Q_LOGICAL;
-
-template <int C> __global__ void __launch_bounds__(Q_THREADS)
-k_combine_q(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail,
-            Xyzz* buckets, uint32_t* long_count, uint32_t* long_list, uint32_t nb)
-{
-    const uint32_t MSM_BUCKETS = nb; // sets x 2^(C-1): every MSM of the batch has its own bucket set
-    const uint32_t total = offsets[MSM_BUCKETS + 1];
-    const uint32_t gl = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    const int q = threadIdx.x & 3;
-    const uint32_t b = gl + 1;
-    if (b > MSM_BUCKETS) return;
-    const uint32_t base = offsets[1];
-    const uint32_t sb = offsets[b], eb = offsets[b + 1];
-    if (sb == eb) {
-        if (q == 0) xyzz_store(buckets + (b - 1), xyzz_inf());
-        return;
-    }
-    const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-    const bool at_start = (sb == base + l0 * seg);
-    if (l0 == l1) {
-        uint32_t seg_end = base + (l0 + 1) * seg;
-        if (seg_end > total || seg_end < base) seg_end = total;
-        if (at_start) { if (q == 0) xyzz_store(buckets + (b - 1), xyzz_load(head + l0)); }
-        else if (eb == seg_end) { if (q == 0) xyzz_store(buckets + (b - 1), xyzz_load(tail + l0)); }
-        return; // else: complete run, already stored
-    }
-    if (l1 - l0 > (uint32_t)MSM_LONG_SPAN) {
-        if (q == 0) {
-            const uint32_t slot = atomicAdd(long_count, 1u);
-            long_list[slot] = b;
-        }
-        return;
-    }
-    Xyzz acc = bucket_piece(head, tail, l0, l0, at_start);
-    for (uint32_t l = l0 + 1; l <= l1; l++) acc = xyzz_add_q4(acc, xyzz_load(head + l), q);
-    if (q == 0) xyzz_store(buckets + (b - 1), acc);
-}
-
-// MSM_COMBINE_LANES logical lanes (16 threads) per bucket, butterfly across the logical lanes (shuffle distances 8 and 4)
-template <int C> __global__ void __launch_bounds__(Q_THREADS)
-k_combine_lanes_q(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail,
-                  Xyzz* buckets, uint32_t* long_count, uint32_t* long_list, uint32_t nb)
-{
-    const uint32_t MSM_BUCKETS = nb; // sets x 2^(C-1): every MSM of the batch has its own bucket set
-    const uint32_t total = offsets[MSM_BUCKETS + 1];
-    const uint32_t gl = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    const int q = threadIdx.x & 3;
-    const uint32_t b = gl / MSM_COMBINE_LANES + 1;
-    const uint32_t r = gl % MSM_COMBINE_LANES;
-    if (b > MSM_BUCKETS) return; // whole waves drop out together (64 threads = 4 buckets)
-    const uint32_t base = offsets[1];
-    const uint32_t sb = offsets[b], eb = offsets[b + 1];
-    bool store = true, reduce = false;
-    Xyzz acc = xyzz_inf();
-    if (sb != eb) {
-        const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-        const bool at_start = (sb == base + l0 * seg);
-        if (l0 == l1) {
-            uint32_t seg_end = base + (l0 + 1) * seg;
-            if (seg_end > total || seg_end < base) seg_end = total;
-            if (at_start) acc = xyzz_load(head + l0);
-            else if (eb == seg_end) acc = xyzz_load(tail + l0);
-            else store = false; // complete run, already written by k_accumulate
-        } else if (l1 - l0 > (uint32_t)MSM_LONG_SPAN) {
-            if (r == 0 && q == 0) {
-                const uint32_t slot = atomicAdd(long_count, 1u);
-                long_list[slot] = b;
-            }
-            store = false;
-        } else {
-            reduce = true;
-            for (uint32_t l = l0 + r; l <= l1; l += MSM_COMBINE_LANES) acc = xyzz_add_q4(acc, bucket_piece(head, tail, l, l0, at_start), q);
-        }
-    }
-    if (!reduce && !(sb != eb && store)) acc = xyzz_inf();
-    const unsigned long long any = __ballot(reduce);
-    if (any) {
-        Xyzz part = reduce ? acc : xyzz_inf();
-        for (int m = MSM_COMBINE_LANES >> 1; m >= 1; m >>= 1) part = xyzz_add_q4(part, xyzz_shfl_xor(part, 4 * m), q);
-        if (reduce) acc = part;
-    }
-    if (store && r == 0 && q == 0) xyzz_store(buckets + (b - 1), acc);
-}
-
-template <int C> __global__ void __launch_bounds__(Q_THREADS)
-k_combine_long_q(const uint32_t* __restrict__ offsets, uint32_t seg, const Xyzz* __restrict__ head, const Xyzz* __restrict__ tail, Xyzz* buckets,
-                 const uint32_t* __restrict__ long_count, const uint32_t* __restrict__ long_list)
-{
-    __shared__ Xyzz sm[Q_LOGICAL / 2];
-    const int lt = threadIdx.x >> 2, q = threadIdx.x & 3;
-    const uint32_t cnt = *long_count;
-    const uint32_t base = offsets[1];
-    for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) {
-        const uint32_t b = long_list[i];
-        const uint32_t sb = offsets[b], eb = offsets[b + 1];
-        const uint32_t l0 = (sb - base) / seg, l1 = (eb - 1 - base) / seg;
-        const bool at_start = (sb == base + l0 * seg);
-        Xyzz acc = xyzz_inf();
-        for (uint32_t l = l0 + lt; l <= l1; l += Q_LOGICAL) acc = xyzz_add_q4(acc, bucket_piece(head, tail, l, l0, at_start), q);
-        acc = block_reduce_q4(acc, sm, Q_LOGICAL);
-        if (threadIdx.x == 0) xyzz_store(buckets + (b - 1), acc);
-        __syncthreads();
     }
 }
 
@@ -1155,25 +1037,33 @@ template <int C, int QL> __global__ void __launch_bounds__(4 * QL) k_rowcol_q(co
     }
 }
 
-template <int C> __global__ void __launch_bounds__(Q_THREADS) k_final_planes_q(const Xyzz* __restrict__ rows, const Xyzz* __restrict__ cols, Xyzz* planes)
+// sum_b b*B_b = COLS * sum_hi hi*Row_hi + sum_lo (lo+1)*Col_lo = sum_t 2^t H_t with the bit planes
+//   H_t = sum_{lo : bit t of (lo+1)} Col_lo  +  sum_{hi : bit (t - log_cols) of hi} Row_hi        (t = 0 .. C-2).
+// One block per bit plane: tree-sum the selected rows/columns, then t doublings by one lane -- the planes run side by
+// side, so the serial depth is ~9 additions + t doublings instead of a double-and-add on top of a tree plus log_cols more
+// doublings.  k_final_sum adds the planes and converts to the reference's Jacobian layout.
+template <int C, class Form> __global__ void __launch_bounds__(ReduceBlock<Form>::threads, ReduceBlock<Form>::min_waves)
+k_final_planes(const Xyzz* __restrict__ rows, const Xyzz* __restrict__ cols, Xyzz* planes)
 {
     constexpr int ROWS = 1 << MsmCfg<C>::log_rows, COLS = 1 << MsmCfg<C>::log_cols, LOGC = MsmCfg<C>::log_cols;
-    __shared__ Xyzz sm[Q_LOGICAL / 2];
-    const int t = blockIdx.x, lt = threadIdx.x >> 2, q = threadIdx.x & 3;
+    constexpr int LOGICAL = ReduceBlock<Form>::logical;
+    __shared__ Xyzz sm[LOGICAL / 2];
+    const Form f{};
+    const int t = blockIdx.x, lt = (int)f.lane(threadIdx.x);
     rows += (size_t)blockIdx.y * ROWS;
     cols += (size_t)blockIdx.y * COLS;
     planes += (size_t)blockIdx.y * MSM_MAX_PLANES;
     Xyzz v = xyzz_inf();
     if (t <= LOGC)
-        for (int lo = lt; lo < COLS; lo += Q_LOGICAL)
-            if (((lo + 1) >> t) & 1) v = xyzz_add_q4(v, xyzz_load(cols + lo), q);
+        for (int lo = lt; lo < COLS; lo += LOGICAL)
+            if (((lo + 1) >> t) & 1) v = f.add(v, xyzz_load(cols + lo));
     if (t >= LOGC)
-        for (int hi = lt; hi < ROWS; hi += Q_LOGICAL)
-            if ((hi >> (t - LOGC)) & 1) v = xyzz_add_q4(v, xyzz_load(rows + hi), q);
-    v = block_reduce_q4(v, sm, Q_LOGICAL);
+        for (int hi = lt; hi < ROWS; hi += LOGICAL)
+            if ((hi >> (t - LOGC)) & 1) v = f.add(v, xyzz_load(rows + hi));
+    v = f.block_reduce(v, sm, LOGICAL);
     if (lt == 0) {
-        for (int k = 0; k < t; k++) v = xyzz_dbl_q4(v, q);
-        if (q == 0) xyzz_store(planes + t, v);
+        for (int k = 0; k < t; k++) v = f.dbl(v);
+        if (f.stores()) xyzz_store(planes + t, v);
     }
 }
 
@@ -1285,6 +1175,17 @@ static inline int msm_ensure_aux_streams(bbg_ctx* ctx)
     }
     ctx->aux_stream = ctx->aux_streams[0];
     return BBG_OK;
+}
+
+// The kernel of a stage in the form its option selects, with what the launch derives from the form: threads per logical lane and the
+// block size of the reduce-phase kernels (ReduceBlock).
+template <class Fn> struct FormStage {
+    Fn kernel;
+    unsigned per_lane, block;
+};
+template <class Fn> static FormStage<Fn> stage_in_form(bool quad, Fn four, Fn one)
+{
+    return quad ? FormStage<Fn>{four, EcQuad::threads, ReduceBlock<EcQuad>::threads} : FormStage<Fn>{one, EcLane::threads, ReduceBlock<EcLane>::threads};
 }
 
 template <int C>
@@ -1465,16 +1366,16 @@ int msm_run_c(bbg_ctx* ctx, const Srs& srs, const void* table_v, int sets, const
         ProfScope ps(ctx, "msm_accumulate", st);
         if (ctx->msm_sort != 1) BBG_HIP(hipMemsetAsync(long_count, 0, 8, st)); // the partition sort's scan kernel clears both counts
         // few lanes (n <= 2^14 or so): the kernel's time is one lane's chain of dependent mixed additions -- four threads per lane shorten it
-        if (ctx->msm_accumulate_quad && L.lanes <= MSM_QUAD_ACC_MAX_LANES)
-            hipLaunchKernelGGL(k_accumulate_q4<C>, dim3(grid_for(L.lanes * 4, 256)), dim3(256), 0, st, svals, offsets, table, srs.n, L.seg, head, tail,
-                               buckets, nbuckets);
-        else if (ctx->msm_limbs29) {
+        const bool quad_acc = ctx->msm_accumulate_quad && L.lanes <= MSM_QUAD_ACC_MAX_LANES;
+        if (ctx->msm_limbs29 && !quad_acc) {
             redo_pending = true;
             hipLaunchKernelGGL(k_accumulate29<C>, dim3(grid_for(L.lanes, 256)), dim3(256), 0, st, svals, offsets, table, srs.n, L.seg, head, tail, buckets,
                                redo, nbuckets);
-        } else
-            hipLaunchKernelGGL(k_accumulate<C>, dim3(grid_for(L.lanes, 256)), dim3(256), 0, st, svals, offsets, table, srs.n, L.seg, head, tail, buckets,
-                               nbuckets);
+        } else {
+            const auto acc = stage_in_form(quad_acc, k_accumulate<C, EcQuad>, k_accumulate<C, EcLane>);
+            hipLaunchKernelGGL(acc.kernel, dim3(grid_for(L.lanes * acc.per_lane, 256)), dim3(256), 0, st, svals, offsets, table, srs.n, L.seg, head, tail,
+                               buckets, nbuckets);
+        }
     }
     if (overlap) {
         BBG_HIP(hipEventRecord(ctx->ev_acc[slot], st));
@@ -1483,33 +1384,23 @@ int msm_run_c(bbg_ctx* ctx, const Srs& srs, const void* table_v, int sets, const
     {
         ProfScope ps(ctx, "msm_reduce", rst);
         // msm_reduce_quad: bit 0 combine, bit 1 row/column sums, bit 2 bit planes, bit 3 plane sum -- each stage either with four lanes per EC
-        // operation (curve_quad.hip.h: the same chain, ~3x shorter in time) or with one (the round-1 kernels, kept for A/B)
+        // operation (curve_quad.hip.h: the same chain, ~3x shorter in time) or with one (the round-1 form, kept for A/B)
         const int quad = ctx->msm_reduce_quad;
-        if (quad & 1) {
-            if (L.lanes > (size_t)2 * nbuckets)
-                hipLaunchKernelGGL(k_combine_lanes_q<C>, dim3(grid_for((size_t)nbuckets * MSM_COMBINE_LANES * 4, Q_THREADS)), dim3(Q_THREADS), 0, rst,
-                                   offsets, L.seg, head, tail, buckets, long_count, long_list, nbuckets);
-            else
-                hipLaunchKernelGGL(k_combine_q<C>, dim3(grid_for((size_t)nbuckets * 4, Q_THREADS)), dim3(Q_THREADS), 0, rst, offsets, L.seg, head, tail,
-                                   buckets, long_count, long_list, nbuckets);
-            hipLaunchKernelGGL(k_combine_long_q<C>, dim3(256), dim3(Q_THREADS), 0, rst, offsets, L.seg, head, tail, buckets, long_count, long_list);
-        } else {
-            if (L.lanes > (size_t)2 * nbuckets) // several pieces per bucket: lane groups + butterfly; else one lane per bucket
-                hipLaunchKernelGGL(k_combine_lanes<C>, dim3(grid_for((size_t)nbuckets * MSM_COMBINE_LANES, 256)), dim3(256), 0, rst, offsets,
-                                   L.seg, head, tail, buckets, long_count, long_list, nbuckets);
-            else
-                hipLaunchKernelGGL(k_combine<C>, dim3(grid_for((size_t)nbuckets, 256)), dim3(256), 0, rst, offsets, L.seg, head, tail,
-                                   buckets, long_count, long_list, nbuckets);
-            hipLaunchKernelGGL(k_combine_long<C>, dim3(256), dim3(256), 0, rst, offsets, L.seg, head, tail, buckets, long_count, long_list);
-        }
+        // several pieces per bucket (lanes > 2 x buckets): lane groups + butterfly; else one logical lane per bucket
+        const bool groups = L.lanes > (size_t)2 * nbuckets;
+        const auto comb = groups ? stage_in_form(quad & 1, k_combine_lanes<C, EcQuad>, k_combine_lanes<C, EcLane>) : stage_in_form(quad & 1, k_combine_q<C>, k_combine<C>);
+        hipLaunchKernelGGL(comb.kernel, dim3(grid_for((size_t)nbuckets * (groups ? MSM_COMBINE_LANES : 1) * comb.per_lane, comb.block)), dim3(comb.block), 0,
+                           rst, offsets, L.seg, head, tail, buckets, long_count, long_list, nbuckets);
+        const auto comb_long = stage_in_form(quad & 1, k_combine_long<C, EcQuad>, k_combine_long<C, EcLane>);
+        hipLaunchKernelGGL(comb_long.kernel, dim3(256), dim3(comb_long.block), 0, rst, offsets, L.seg, head, tail, buckets, long_count, long_list);
         if (redo_pending) hipLaunchKernelGGL(k_redo<C>, dim3(128), dim3(256), 0, rst, svals, offsets, table, srs.n, redo, buckets);
         // 64 logical lanes per row / column (measured against 128 / 32 / 16: reduce phase 0.458 / 0.49 / 0.53 / 0.55 ms at 2^20 stand-alone,
         // 0.154 / 0.165 / 0.164 / 0.184 at 2^10; bench step equal for 64 and 128, worse below)
         const dim3 rc_grid((1 << K::log_rows) + (1 << K::log_cols), sets);
         if (quad & 2) hipLaunchKernelGGL((k_rowcol_q<C, BBG_ROWCOL_QL>), rc_grid, dim3(4 * BBG_ROWCOL_QL), 0, rst, buckets, rows, cols);
         else hipLaunchKernelGGL(k_rowcol<C>, rc_grid, dim3(256), 0, rst, buckets, rows, cols);
-        if (quad & 4) hipLaunchKernelGGL(k_final_planes_q<C>, dim3(K::planes, sets), dim3(Q_THREADS), 0, rst, rows, cols, planes);
-        else hipLaunchKernelGGL(k_final_planes<C>, dim3(K::planes, sets), dim3(256), 0, rst, rows, cols, planes);
+        const auto fin = stage_in_form(quad & 4, k_final_planes<C, EcQuad>, k_final_planes<C, EcLane>);
+        hipLaunchKernelGGL(fin.kernel, dim3(K::planes, sets), dim3(fin.block), 0, rst, rows, cols, planes);
         // (the plane sum stays a launch of its own: folded into the planes kernel as "the last block to finish adds the planes", its
         // device-scope fences write back and invalidate the L2 of every XCD a block runs on -- the accumulation running beside it lost
         // 2 % (1.120 vs 1.098 ms, bench step 1.672 vs 1.647), and a small MSM gained nothing: 87-98 us against 64 + 20)

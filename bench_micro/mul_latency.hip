@@ -1,5 +1,5 @@
 // LATENCY of one Montgomery product on gfx950 when a wave is ALONE on its SIMD -- the regime of the MSM reduce chains (k_combine*, k_rowcol_q,
-// k_final_planes_q, k_final_sum_q: a few waves running a chain of dependent EC operations; a third of a small MSM, msm_kernels.hip.h).
+// k_final_planes, k_final_sum in their four-thread form: a few waves running a chain of dependent EC operations; a third of a small MSM, msm_kernels.hip.h).
 // bench_micro/mul29.hip and mulbench.hip measure THROUGHPUT (many waves per SIMD); here every product waits for the one before it.
 //   fe_mul        8 x 32-bit limbs, one mad + one addc per limb product, columns strictly one after the other (field.hip.h)
 //   fe_mul29      the same product through the 29-bit multiplier, columns as asm chains (field29.hip.h)

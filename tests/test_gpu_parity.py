@@ -10,6 +10,8 @@ import pytest
 
 from conftest import limbs, sha, unhex
 import callback_engines  # tests/tools: Python stand-ins for work-queue callbacks (test tooling)
+import coarse_inputs as ci  # tests/tools: big-integer models and range checks of the coarse field representation
+import msm_closed_forms as cf  # tests/tools: MSM input families with closed-form results, and the launch shape restated
 from msm_options import msm_options  # tests/tools: MSM options set for a block, library defaults restored
 
 pytestmark = pytest.mark.gpu
@@ -495,6 +497,55 @@ def test_msm_option_matrix_is_bit_identical(pkg, oracle, bbg, srs16):
                     with msm_options(bbg, msm_reduce_quad=quad, msm_upload_pieces=pieces, msm_async_reduce=overlap):
                         got = oracle.jac_to_affine(bbg.msm(srs, sc))
                     assert np.array_equal(got, want), (n, quad, pieces, overlap)
+
+
+def test_msm_forms_on_skewed_small_inputs(pkg, oracle, bbg, srs16):
+    """Both forms of every accumulate / reduce stage (one thread per EC operation, or four) on inputs whose buckets are of every kind the
+    combine kernels tell apart, at sizes of a few milliseconds.  Uniform scalars at n <= 2^16 leave the long-bucket queue empty and every
+    bucket a few lanes short; here, with msm_window = 13 forced (20 windows, 4096 buckets, seg 8):
+      n = 1024: 2560 lanes <= 2 x buckets, so k_combine or its four-thread form runs; n = 4096: 10 240 lanes, so k_combine_lanes in either form.
+      D (all scalars equal: one bucket per window over 128 / 512 lanes, k_combine_long), E (three scalars: ~43 lanes = pieces, ~171 = long),
+      G8 (one window, seven buckets), B_cancel (infinity), I (points at infinity; uniform scalars: head, tail and complete runs) and 16
+      scalars by residue mod 16 (8 / 32 lanes per bucket: several pieces below MSM_LONG_SPAN).
+    msm_reduce_quad 0 / 14 / 15 x the three accumulation kernels: every result is the family's closed form (tests/tools/msm_closed_forms.py,
+    checked against oracle.msm_naive by the CPU suite), and the nine results of a case are one affine point."""
+    for n, combine in ((1024, "k_combine"), (4096, "k_combine_lanes")):
+        shape = cf.msm_shape(n, c=13)
+        assert (shape["windows"], shape["seg"], shape["lanes"], shape["combine"]) == (20, 8, 20 * n // 8, combine)
+        assert (shape["lanes"] > 2 * cf.msm_buckets(13)) == (combine == "k_combine_lanes")
+        base = srs16.read(0, n)
+        srs_of, cases = {"hashed": srs16}, []  # a hashed case of n terms runs over the first n points of srs16
+        try:
+            for family in ("D", "E", "G8", "B_cancel", "I"):
+                kind = cf.SRS_KIND[family]
+                pts = cf.srs_points(oracle, kind, base)
+                if kind not in srs_of:
+                    srs_of[kind] = bbg.srs_register(pts)
+                cases.append((kind, cf.family_case(oracle, pkg, family, pts, base, 0xF0A5 + n)))
+            v = pkg.synthetic_scalars(0xF0A6 + n, 16)
+            cls = np.arange(n) % 16
+            cases.append(("hashed", cf.Case("mod16", v[cls], cf.class_form(oracle, base, [cf.plain(x) for x in v], cls))))
+            assert cases[3][1].want is None  # B_cancel
+            for kind, case in cases:
+                got = []
+                for quad in (0, 14, 15):
+                    for acc_quad, limbs29 in ((1, 1), (0, 1), (0, 0)):
+                        what = (n, case.family, quad, acc_quad, limbs29)
+                        with msm_options(bbg, msm_window=13, msm_reduce_quad=quad, msm_accumulate_quad=acc_quad, msm_limbs29=limbs29):
+                            jac = bbg.msm(srs_of[kind], case.scalars)
+                        ci.assert_coarse_jacobian(jac, str(what))
+                        got.append(None if int(jac[3]) >> 63 else oracle.jac_to_affine(jac))
+                        if case.want is None:
+                            assert got[-1] is None, what
+                        else:
+                            assert got[-1] is not None and np.array_equal(got[-1], case.want), what
+                assert len(got) == 9
+                for g in got[1:]:
+                    assert (g is None and got[0] is None) or np.array_equal(g, got[0]), (n, case.family)
+        finally:
+            for kind, s in srs_of.items():
+                if kind != "hashed":
+                    s.free()
 
 
 def test_msm_limbs29_degenerate_runs(pkg, oracle, bbg, srs16):

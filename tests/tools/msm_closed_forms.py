@@ -28,13 +28,13 @@ Case = collections.namedtuple("Case", "family scalars want")
 
 # ---------------------------------------------------------------------------------------------- restatement of the launch shape
 CHIP_LANES = 65536      # msm_kernels.hip.h msm_seg_len: 256 CUs x 4 SIMDs x 64
-MSM_SEG_MIN, MSM_SEG_DEFAULT = 8, 64  # msm_kernels.hip.h:530
-MSM_LONG_SPAN = 48      # msm_kernels.hip.h:532: buckets spanning more lanes go to k_combine_long
+MSM_SEG_MIN, MSM_SEG_DEFAULT = 8, 64  # msm_kernels.hip.h, the constants of the same names
+MSM_LONG_SPAN = 48      # msm_kernels.hip.h MSM_LONG_SPAN: buckets spanning more lanes go to k_combine_long (bucket_classify)
 MSM_TINY_WIDTH = 8
 
 
 def msm_auto_window(n):
-    """msm.hip:282 msm_auto_window (MSM_SMALL_WINDOW_MAX_LOG2N = 14, MSM_TINY_MAX_LOG2N = 13)."""
+    """msm.hip msm_auto_window (MSM_SMALL_WINDOW_MAX_LOG2N = 14, MSM_TINY_MAX_LOG2N = 13)."""
     if n >= 1 << 23:
         return 22
     if n >= 1 << 21:
@@ -58,7 +58,7 @@ def msm_buckets(c):
 
 
 def msm_seg_len(entries, buckets, waves_override=0):
-    """msm_kernels.hip.h:1239 msm_seg_len: entries per accumulation lane segment (buckets = sets x 2^(C-1))."""
+    """msm_kernels.hip.h msm_seg_len: entries per accumulation lane segment (buckets = sets x 2^(C-1))."""
     max_waves = waves_override if waves_override > 0 else 6
     if entries <= MSM_SEG_MIN * 4 * CHIP_LANES:
         return MSM_SEG_MIN
@@ -78,8 +78,8 @@ def msm_seg_len(entries, buckets, waves_override=0):
 
 def msm_shape(n, c=None, waves=0, sets=1, total_n=None):
     """What an n-term MSM (or a batch of `sets` of total_n terms) runs with: window, windows, seg, lanes and the default one-lane combine
-    kernel (msm_kernels.hip.h:1532: k_combine_lanes when lanes > 2 x buckets, else k_combine; the four-lane forms of msm_reduce_quad bit 0
-    choose alike, :1524).  Only used to pick option values and to document what a case reaches, never to compute a result."""
+    kernel (msm_kernels.hip.h msm_run_c, `groups`: k_combine_lanes when lanes > 2 x buckets, else k_combine; the four-thread forms of
+    msm_reduce_quad bit 0, k_combine_lanes<C, EcQuad> and k_combine_q, are chosen by the same test).  Only used to pick option values and to document what a case reaches, never to compute a result."""
     c = c or msm_auto_window(n)
     total_n = n if total_n is None else total_n
     entries = total_n * msm_windows(c)
