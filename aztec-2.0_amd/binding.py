@@ -144,6 +144,13 @@ def load_library():
         "bbg_poly_evaluate_lagrange_device": (cint, [vp, vp, vp, sz, ctypes.c_uint, vp, vp]),
         "bbg_poly_evaluate_lagrange": (cint, [vp, vp, ctypes.c_uint, vp, vp]),
         "bbg_kate_opening_lagrange_device": (cint, [vp, vp, vp, ctypes.c_uint, vp, vp]),
+        "bbg_open_points_device": (cint, [vp, vp, ctypes.c_uint, vp, vp, sz, vp, vp]),
+        "bbg_open_points": (cint, [vp, vp, ctypes.c_uint, vp, vp, sz, vp, vp]),
+        "bbg_open_points_set_budget": (cint, [vp, sz]),
+        "bbg_kzg_verify_reduce_device": (cint, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "bbg_kzg_verify_reduce": (cint, [vp, vp, vp, vp, vp, sz, vp, vp]),
+        "bbg_kzg_verify_device": (cint, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+        "bbg_kzg_verify": (cint, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
         "bbg_dev_alloc": (cint, [vp, sz, ctypes.POINTER(vp)]),
         "bbg_dev_free": (cint, [vp, vp]),
         "bbg_dev_upload": (cint, [vp, vp, vp, sz]),
@@ -214,6 +221,8 @@ EXPORTED_SYMBOLS = [
     "bbg_g1_msm", "bbg_g1_msm_device", "bbg_g1_msm_plan",
     "bbg_g2_mul", "bbg_g2_lines_prepare", "bbg_g2_lines_pairs", "bbg_g2_lines_read", "bbg_g2_lines_free",
     "bbg_pairing_product_device", "bbg_pairing_product", "bbg_pairing_product_wave_device", "bbg_pairing_product_wave",
+    "bbg_open_points_device", "bbg_open_points", "bbg_open_points_set_budget",
+    "bbg_kzg_verify_reduce_device", "bbg_kzg_verify_reduce", "bbg_kzg_verify_device", "bbg_kzg_verify",
 ]
 
 
@@ -856,6 +865,76 @@ class Bbg:
         self._ck(self.lib.bbg_kate_opening_lagrange_device(self.ctx, ctypes.c_void_p(d_evals), ctypes.c_void_p(d_dest), log2n, zz.ctypes.data,
                                                            out.ctypes.data))
         return out
+
+    # ---- many Lagrange-form polynomials, each opened at its own point (csrc/open_points.hip)
+    def open_points(self, lagrange, evals, z, proofs=True):
+        """(y, proofs) for (count, n, 4) Montgomery values and (count, 4) points: y[k] = F_k(z[k]) as (count, 4) canonical words and
+        proofs[k] = the commitment over `lagrange` (an Srs in Lagrange form) to (F_k(X) - y[k]) / (X - z[k]) as (count, 8) canonical affine
+        words.  proofs=False evaluates only: `lagrange` may be None and the second result is None (bbg_open_points)."""
+        e = np.ascontiguousarray(evals, dtype=np.uint64)
+        if e.ndim != 3 or e.shape[0] < 1 or e.shape[2] != 4 or e.shape[1] & (e.shape[1] - 1) or e.shape[1] < 2:
+            raise ValueError(f"expected (count, 2^k, 4) uint64 limbs, got {e.shape}")
+        zz = _u64(z, 4)
+        if zz.shape[0] != e.shape[0]:
+            raise ValueError("one point per polynomial")
+        count, log2n = e.shape[0], e.shape[1].bit_length() - 1
+        y = np.zeros((count, 4), dtype=np.uint64)
+        out = np.zeros((count, 8), dtype=np.uint64) if proofs else None
+        self._ck(self.lib.bbg_open_points(self.ctx, lagrange.handle if lagrange is not None else None, log2n, e.ctypes.data, zz.ctypes.data, count,
+                                          y.ctypes.data, out.ctypes.data if proofs else None))
+        return y, out
+
+    def open_points_device(self, lagrange, log2n, d_evals, d_z, count, d_y, d_proofs=None):
+        """Device pointers: count x n x 32 B values and count x 32 B points in, count x 32 B values and (unless None) count x 64 B proofs
+        out; asynchronous on the context stream (bbg_open_points_device)."""
+        self._ck(self.lib.bbg_open_points_device(self.ctx, lagrange.handle if lagrange is not None else None, log2n, ctypes.c_void_p(d_evals),
+                                                 ctypes.c_void_p(d_z), count, ctypes.c_void_p(d_y), ctypes.c_void_p(d_proofs) if d_proofs else None))
+
+    def open_points_set_budget(self, nbytes):
+        """The bytes a chunk of open_points may take of working memory; 0 = the default of 1 GiB (bbg_open_points_set_budget)."""
+        self._ck(self.lib.bbg_open_points_set_budget(self.ctx, int(nbytes)))
+
+    # ---- openings at arbitrary points reduced to the two points of one pairing check (csrc/kzg_verify.hip)
+    def kzg_verify_reduce(self, commitments, z, y, proofs, rho):
+        """N openings (commitments[i], z[i], y[i], proofs[i]): (2, 8) canonical affine words (L, R); every opening is valid iff
+        e(L, [x]_2) = e(R, [1]_2), up to the choice of rho (4 Montgomery words).  A point off the curve raises BbgError
+        (bbg_kzg_verify_reduce)."""
+        com, prf, zz, yy = _u64(commitments, 8), _u64(proofs, 8), _u64(z, 4), _u64(y, 4)
+        N = com.shape[0]
+        if prf.shape[0] != N or zz.shape[0] != N or yy.shape[0] != N:
+            raise ValueError(f"expected {N} points, values and proofs")
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        out = np.zeros((2, 8), dtype=np.uint64)
+        self._ck(self.lib.bbg_kzg_verify_reduce(self.ctx, com.ctypes.data, zz.ctypes.data, yy.ctypes.data, prf.ctypes.data, N, rho.ctypes.data, out.ctypes.data))
+        return out
+
+    def kzg_verify_reduce_device(self, d_commitments, d_z, d_y, d_proofs, N, rho, d_out, d_off_curve=None):
+        """Device pointers (N x 64 B, N x 32 B, N x 32 B, N x 64 B in; 128 B and, optionally, one uint32 out), rho on the host; asynchronous on
+        the context stream (bbg_kzg_verify_reduce_device)."""
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        self._ck(self.lib.bbg_kzg_verify_reduce_device(self.ctx, ctypes.c_void_p(d_commitments), ctypes.c_void_p(d_z), ctypes.c_void_p(d_y),
+                                                       ctypes.c_void_p(d_proofs), N, rho.ctypes.data, ctypes.c_void_p(d_out),
+                                                       ctypes.c_void_p(d_off_curve) if d_off_curve else None))
+
+    def kzg_verify(self, lines, commitments, z, y, proofs, rho):
+        """The verdict on N openings (arguments as kzg_verify_reduce) against `lines`, the G2Lines of ([x]_2, [1]_2): 1 = every opening is
+        valid under rho, 0 = not.  A point off the curve (status 2) raises BbgError (bbg_kzg_verify)."""
+        com, prf, zz, yy = _u64(commitments, 8), _u64(proofs, 8), _u64(z, 4), _u64(y, 4)
+        N = com.shape[0]
+        if prf.shape[0] != N or zz.shape[0] != N or yy.shape[0] != N:
+            raise ValueError(f"expected {N} points, values and proofs")
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        status = ctypes.c_uint32(0)
+        self._ck(self.lib.bbg_kzg_verify(self.ctx, lines.handle, com.ctypes.data, zz.ctypes.data, yy.ctypes.data, prf.ctypes.data, N, rho.ctypes.data,
+                                         ctypes.byref(status)))
+        return int(status.value)
+
+    def kzg_verify_device(self, lines, d_commitments, d_z, d_y, d_proofs, N, rho, d_status):
+        """Device pointers as kzg_verify_reduce_device, d_status one uint32 (1 / 0 / 2); rho on the host; asynchronous on the context stream
+        (bbg_kzg_verify_device)."""
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
+        self._ck(self.lib.bbg_kzg_verify_device(self.ctx, lines.handle, ctypes.c_void_p(d_commitments), ctypes.c_void_p(d_z), ctypes.c_void_p(d_y),
+                                                ctypes.c_void_p(d_proofs), N, rho.ctypes.data, ctypes.c_void_p(d_status)))
 
     # host-buffer forms (what the C++ shim binds evaluate / compute_kate_opening_coefficients / divide_by_pseudo_vanishing_polynomial to)
     def poly_evaluate(self, coeffs, z):

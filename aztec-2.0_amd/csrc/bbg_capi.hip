@@ -1636,6 +1636,112 @@ int bbg_kate_opening_lagrange_device(bbg_ctx* ctx, const void* d_evals, void* d_
     std::lock_guard<std::mutex> lk(ctx->mu);
     return poly_kate_opening_lagrange(ctx, d_evals, d_dest, log2n, z, f_out, ctx->stream);
 }
+
+// ------------------------------------------------------------------------------------------------ many openings, each at its own point (open_points.hip)
+int bbg_open_points_set_budget(bbg_ctx* ctx, size_t bytes)
+{
+    CHECK_CTX(ctx);
+    if (bytes > ((size_t)1 << 36)) { set_error("bbg_open_points_set_budget: at most 2^36 bytes"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->open_points_budget = bytes ? (long)bytes : 1L << 30;
+    return BBG_OK;
+}
+
+int bbg_open_points_device(bbg_ctx* ctx, bbg_srs* lagrange, unsigned log2n, const void* d_evals, const void* d_z, size_t count, void* d_y, void* d_proofs)
+{
+    CHECK_CTX(ctx);
+    BBG_TRY(open_points_check("bbg_open_points_device", ctx, lagrange, log2n, d_evals, d_z, count, d_y, d_proofs));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return open_points_run(ctx, lagrange, log2n, d_evals, d_z, count, d_y, d_proofs, ctx->stream);
+}
+
+int bbg_open_points(bbg_ctx* ctx, bbg_srs* lagrange, unsigned log2n, const uint64_t* evals, const uint64_t* z, size_t count, uint64_t* y, uint64_t* proofs)
+{
+    CHECK_CTX(ctx);
+    BBG_TRY(open_points_check("bbg_open_points", ctx, lagrange, log2n, evals, z, count, y, proofs)); // before the staging buffer is sized by count
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t evals_bytes = (count * 32) << log2n;
+    Staged st(ctx, "bbg_open_points");
+    const auto d_evals = st.region(evals_bytes), d_z = st.region(count, 32), d_y = st.region(count, 32), d_proofs = st.region(proofs ? count : 0, 64);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_evals, evals, evals_bytes));
+    BBG_TRY(st.up(d_z, z, count * 32));
+    BBG_TRY(open_points_run(ctx, lagrange, log2n, st[d_evals], st[d_z], count, st[d_y], proofs ? st[d_proofs] : nullptr, ctx->stream));
+    BBG_TRY(st.down(y, d_y, count * 32));
+    if (proofs) BBG_TRY(st.down(proofs, d_proofs, count * 64));
+    return st.wait();
+}
+
+// ------------------------------------------------------------------------------------------------ openings at arbitrary points to one pairing check (kzg_verify.hip)
+int bbg_kzg_verify_reduce_device(bbg_ctx* ctx, const void* d_commitments, const void* d_z, const void* d_y, const void* d_proofs, size_t N, const uint64_t rho[4],
+                                 void* d_out, void* d_off_curve)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return kzg_verify_reduce(ctx, d_commitments, d_z, d_y, d_proofs, N, rho, d_out, d_off_curve, ctx->stream);
+}
+
+int bbg_kzg_verify_reduce(bbg_ctx* ctx, const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t N, const uint64_t rho[4],
+                          uint64_t out[16])
+{
+    CHECK_CTX(ctx);
+    BBG_TRY(kzg_verify_check("bbg_kzg_verify_reduce", commitments, z, y, proofs, N, rho, out)); // before the staging buffer is sized by N
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    Staged st(ctx, "bbg_kzg_verify_reduce");
+    const auto d_com = st.region(N, 64), d_proofs = st.region(N, 64), d_z = st.region(N, 32), d_y = st.region(N, 32);
+    const auto d_res = st.region(256); // L, R (128 B), then the off-curve count: one block, one download
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_com, commitments, N * 64));
+    BBG_TRY(st.up(d_proofs, proofs, N * 64));
+    BBG_TRY(st.up(d_z, z, N * 32));
+    BBG_TRY(st.up(d_y, y, N * 32));
+    BBG_TRY(kzg_verify_reduce(ctx, st[d_com], st[d_z], st[d_y], st[d_proofs], N, rho, st[d_res], st[d_res] + 128, ctx->stream));
+    uint64_t res[18]; // L, R, then the count in the low word of res[16]
+    BBG_TRY(st.down(res, d_res, 128 + 4));
+    BBG_TRY(st.wait());
+    uint32_t off_curve = 0;
+    memcpy(&off_curve, res + 16, 4);
+    if (off_curve) {
+        set_error("bbg_kzg_verify_reduce: " + std::to_string(off_curve) + " of the commitments and proofs are not on the curve");
+        return BBG_E_INVALID;
+    }
+    memcpy(out, res, 128);
+    return BBG_OK;
+}
+
+int bbg_kzg_verify_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d_commitments, const void* d_z, const void* d_y, const void* d_proofs, size_t N,
+                          const uint64_t rho[4], void* d_status)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return kzg_verify_run(ctx, lines, d_commitments, d_z, d_y, d_proofs, N, rho, d_status, ctx->stream);
+}
+
+int bbg_kzg_verify(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t N,
+                   const uint64_t rho[4], uint32_t* status)
+{
+    CHECK_CTX(ctx);
+    if (!lines) { set_error("bbg_kzg_verify: null argument"); return BBG_E_INVALID; }
+    BBG_TRY(kzg_verify_check("bbg_kzg_verify", commitments, z, y, proofs, N, rho, status)); // before the staging buffer is sized by N
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    Staged st(ctx, "bbg_kzg_verify");
+    const auto d_com = st.region(N, 64), d_proofs = st.region(N, 64), d_z = st.region(N, 32), d_y = st.region(N, 32), d_status = st.region(4);
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_com, commitments, N * 64));
+    BBG_TRY(st.up(d_proofs, proofs, N * 64));
+    BBG_TRY(st.up(d_z, z, N * 32));
+    BBG_TRY(st.up(d_y, y, N * 32));
+    BBG_TRY(kzg_verify_run(ctx, lines, st[d_com], st[d_z], st[d_y], st[d_proofs], N, rho, st[d_status], ctx->stream));
+    uint32_t word = 0;
+    BBG_TRY(st.down(&word, d_status, 4));
+    BBG_TRY(st.wait());
+    *status = word;
+    if (word == 2) {
+        set_error("bbg_kzg_verify: a commitment or a proof is not on the curve");
+        return BBG_E_INVALID;
+    }
+    return BBG_OK;
+}
 int bbg_divide_by_pseudo_vanishing(bbg_ctx* ctx, uint64_t* evals, unsigned log2_src, unsigned log2_target, size_t num_roots_cut)
 {
     CHECK_CTX(ctx);

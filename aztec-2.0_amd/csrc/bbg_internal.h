@@ -223,6 +223,12 @@ struct bbg_ctx {
     // cells_verify.hip: the intermediates of one bbg_cells_verify call (L, R, the packed pair [L, -R], the off-curve count, the pairing's status
     // word): 512 bytes, sized once
     bbg::DevBuf cells_verdict;
+    // open_points.hip: the working set of one chunk of a bbg_open_points call (quotient values, partial sums, hit slots, the MSM's results,
+    // flags), at most open_points_budget bytes unless one polynomial alone needs more
+    bbg::DevBuf open_points_work;
+    long open_points_budget = 1L << 30; // bbg_open_points_set_budget (bytes): what a chunk's working set may take; the tests set it to cross a chunk boundary
+    // kzg_verify.hip: the working set of one bbg_kzg_verify_reduce call: the packed points and scalars, the powers of rho, the partial sums
+    bbg::DevBuf kzg_work;
     int ecntt_mul = 1;               // option "ecntt_mul": 1 = the Lagrange transform's stages multiply with xyzz_mul_glv (default: measured 2.2x at 2^20, profiles/var_base.txt), 0 = with xyzz_mul_fr (A/B)
 };
 
@@ -230,7 +236,7 @@ struct bbg_ctx {
 constexpr bbg::DevBuf bbg_ctx::* BBG_CTX_SCRATCH[] = {
     &bbg_ctx::ntt_scratch, &bbg_ctx::staging,  &bbg_ctx::poly_scratch, &bbg_ctx::gp_totals,  &bbg_ctx::quot_setup,
     &bbg_ctx::fb_table,    &bbg_ctx::vb_tables, &bbg_ctx::ecntt_work,   &bbg_ctx::cells_work, &bbg_ctx::msm_points_work,
-    &bbg_ctx::pairing_work, &bbg_ctx::cells_verdict,
+    &bbg_ctx::pairing_work, &bbg_ctx::cells_verdict, &bbg_ctx::open_points_work, &bbg_ctx::kzg_work,
 };
 
 // bbg_open_all_prepare[_cells] (open_all.hip), l = 2^log2cell, r = n / l: the l transforms at 2r of the string's residue classes (l = 1:
@@ -444,4 +450,30 @@ int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log
 int cells_verify_run(bbg_ctx* ctx, bbg_srs* srs, const struct bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
                      const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho,
                      void* d_status, hipStream_t stream);
+// the verdict's steps, shared with kzg_verify.hip: the handle's checks (BBG_E_INVALID with the error text set; `first`: what the handle's
+// first point is called), ctx->cells_verdict with the places a reduction writes (L, R) and its off-curve count to, and the tail behind such a
+// reduction: k_cv_pack, the wave pairing at count 1, k_cv_verdict to *d_status.  The tail queues only.
+int cells_verdict_check(const char* who, const bbg_ctx* ctx, const struct bbg_g2_lines* lines, const char* first);
+int cells_verdict_buffer(bbg_ctx* ctx, void** d_lr, void** d_off_curve);
+int cells_verdict_run(bbg_ctx* ctx, const struct bbg_g2_lines* lines, void* d_status, hipStream_t stream);
+// open_points.hip.  poly.hip's check of either form's arguments (device or host arrays; `proofs` null = evaluation only, and
+// `lagrange` may then be null): BBG_E_INVALID with the error text set, nothing queued.
+int open_points_check(const char* who, const bbg_ctx* ctx, const bbg_srs* lagrange, unsigned log2n, const void* evals, const void* z, size_t count, const void* y,
+                      const void* proofs);
+// the working set of one polynomial, and the polynomials one chunk holds under the context's budget
+size_t open_points_poly_bytes(unsigned log2n, bool proofs);
+size_t open_points_chunk(const bbg_ctx* ctx, unsigned log2n, bool proofs, size_t count);
+// d_y[k] = F_k(d_z[k]) and, with d_proofs, d_proofs[k] = the commitment over `lagrange` to (F_k(X) - y_k) / (X - z_k); arguments already
+// checked.  Queues only once the working memory has its size.
+int open_points_run(bbg_ctx* ctx, bbg_srs* lagrange, unsigned log2n, const void* d_evals, const void* d_z, size_t count, void* d_y, void* d_proofs,
+                    hipStream_t stream);
+// kzg_verify.hip.  The argument checks that look at no overlap: BBG_E_INVALID with the error text set.
+int kzg_verify_check(const char* who, const void* commitments, const void* z, const void* y, const void* proofs, size_t N, const uint64_t* rho, const void* out);
+// d_out[0] = L = sum_i rho^i pi_i, d_out[1] = R = sum_i rho^i (C_i - [y_i] G + [z_i] pi_i) (canonical affine, aff_inf() for infinity);
+// *d_off_curve (may be null) = the finite commitments and proofs that are not on the curve.  Queues only.
+int kzg_verify_reduce(bbg_ctx* ctx, const void* d_commitments, const void* d_z, const void* d_y, const void* d_proofs, size_t N, const uint64_t* rho,
+                      void* d_out, void* d_off_curve, hipStream_t stream);
+// *d_status as cells_verify_run writes it; `lines`: the handle of ([x]_2, [1]_2)
+int kzg_verify_run(bbg_ctx* ctx, const struct bbg_g2_lines* lines, const void* d_commitments, const void* d_z, const void* d_y, const void* d_proofs, size_t N,
+                   const uint64_t* rho, void* d_status, hipStream_t stream);
 } // namespace bbg

@@ -321,22 +321,25 @@ __global__ void __launch_bounds__(64) k_cv_verdict(const unsigned* __restrict__ 
 // the layout of ctx->cells_verdict
 constexpr size_t CVV_LR = 0, CVV_PAIR = 128, CVV_OFF = 256, CVV_PAIRED = 260, CVV_BYTES = 512;
 
-int cells_verify_run(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
-                     const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho,
-                     void* d_status, hipStream_t st)
+// The verdict's steps, shared with kzg_verify.hip: the handle's checks (`first`: what its first point is called), the buffer with the places
+// of (L, R) and of the off-curve count, and the tail behind a reduction that wrote both there.
+int cells_verdict_check(const char* who, const bbg_ctx* ctx, const bbg_g2_lines* lines, const char* first)
 {
-    const std::string who("bbg_cells_verify_device");
-    if (!lines || !d_status || !d_commitments || !d_values || !d_proofs) { set_error(who + ": null argument"); return BBG_E_INVALID; }
-    if (lines->pairs != 2) { set_error(who + ": the lines handle must hold exactly two points, [x^l]_2 and [1]_2"); return BBG_E_INVALID; }
-    if (lines->device != ctx->device) { set_error(who + ": the handle was made on another device"); return BBG_E_INVALID; }
-    if (int rc = cells_verify_check(who.c_str(), ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho)) return rc;
-    const struct { const void* p; size_t bytes; } ins[3] = { { d_commitments, ncom * 64 }, { d_values, (K * 32) << log2cell }, { d_proofs, K * 64 } };
-    for (const auto& in : ins)
-        if (ranges_overlap(d_status, 4, in.p, in.bytes)) { set_error(who + ": the status word overlaps an input"); return BBG_E_INVALID; }
+    const std::string w(who);
+    if (lines->pairs != 2) { set_error(w + ": the lines handle must hold exactly two points, " + first + " and [1]_2"); return BBG_E_INVALID; }
+    if (lines->device != ctx->device) { set_error(w + ": the handle was made on another device"); return BBG_E_INVALID; }
+    return BBG_OK;
+}
+int cells_verdict_buffer(bbg_ctx* ctx, void** d_lr, void** d_off_curve)
+{
     if (int rc = ctx->cells_verdict.ensure(CVV_BYTES)) return rc;
+    *d_lr = (char*)ctx->cells_verdict.p + CVV_LR;
+    *d_off_curve = (char*)ctx->cells_verdict.p + CVV_OFF;
+    return BBG_OK;
+}
+int cells_verdict_run(bbg_ctx* ctx, const bbg_g2_lines* lines, void* d_status, hipStream_t st)
+{
     char* v = (char*)ctx->cells_verdict.p;
-    if (int rc = cells_verify_reduce(ctx, srs, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, v + CVV_LR, v + CVV_OFF, st))
-        return rc;
     {
         ProfScope ps(ctx, "cells_verify_pack", st);
         hipLaunchKernelGGL(k_cv_pack, dim3(1), dim3(64), 0, st, (const Affine*)(v + CVV_LR), (Affine*)(v + CVV_PAIR));
@@ -348,6 +351,23 @@ int cells_verify_run(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsi
     }
     BBG_HIP(hipGetLastError());
     return BBG_OK;
+}
+
+int cells_verify_run(bbg_ctx* ctx, bbg_srs* srs, const bbg_g2_lines* lines, unsigned log2n, unsigned log2cell, const void* d_commitments, size_t ncom,
+                     const uint32_t* commitment_ids, const uint32_t* cell_ids, size_t K, const void* d_values, const void* d_proofs, const uint64_t* rho,
+                     void* d_status, hipStream_t st)
+{
+    const std::string who("bbg_cells_verify_device");
+    if (!lines || !d_status || !d_commitments || !d_values || !d_proofs) { set_error(who + ": null argument"); return BBG_E_INVALID; }
+    if (int rc = cells_verdict_check(who.c_str(), ctx, lines, "[x^l]_2")) return rc;
+    if (int rc = cells_verify_check(who.c_str(), ctx, srs, log2n, log2cell, ncom, commitment_ids, cell_ids, K, rho)) return rc;
+    const struct { const void* p; size_t bytes; } ins[3] = { { d_commitments, ncom * 64 }, { d_values, (K * 32) << log2cell }, { d_proofs, K * 64 } };
+    for (const auto& in : ins)
+        if (ranges_overlap(d_status, 4, in.p, in.bytes)) { set_error(who + ": the status word overlaps an input"); return BBG_E_INVALID; }
+    void *lr = nullptr, *off = nullptr;
+    if (int rc = cells_verdict_buffer(ctx, &lr, &off)) return rc;
+    if (int rc = cells_verify_reduce(ctx, srs, log2n, log2cell, d_commitments, ncom, commitment_ids, cell_ids, K, d_values, d_proofs, rho, lr, off, st)) return rc;
+    return cells_verdict_run(ctx, lines, d_status, st);
 }
 
 } // namespace bbg

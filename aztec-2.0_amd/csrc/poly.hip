@@ -622,6 +622,27 @@ int poly_kate_opening_lagrange(bbg_ctx* ctx, const void* d_evals, void* d_dest, 
     BBG_HIP(hipStreamSynchronize(st));
     return BBG_OK;
 }
+// bbg_open_points[_device] (open_points.hip): every refusal, decided before anything is queued
+int open_points_check(const char* who, const bbg_ctx* ctx, const bbg_srs* lagrange, unsigned log2n, const void* evals, const void* z, size_t count, const void* y,
+                      const void* proofs)
+{
+    const std::string w(who);
+    if (!evals || !z || !y || (proofs && !lagrange)) { set_error(w + ": null argument"); return BBG_E_INVALID; }
+    if (int rc = check_log2n(who, log2n, 1, 28)) return rc;
+    if (count < 1 || count > ((size_t)1 << 20)) { set_error(w + ": count must be 1 .. 2^20"); return BBG_E_INVALID; }
+    if (proofs) {
+        if (int rc = check_srs_holds(who, lagrange->s, log2n)) return rc;
+        if (int rc = check_srs_device(who, lagrange->s, ctx)) return rc;
+    }
+    const size_t evals_bytes = (count * 32) << log2n, y_bytes = count * 32, proofs_bytes = count * 64;
+    if (ranges_overlap(y, y_bytes, evals, evals_bytes) || ranges_overlap(y, y_bytes, z, count * 32) ||
+        (proofs && (ranges_overlap(proofs, proofs_bytes, evals, evals_bytes) || ranges_overlap(proofs, proofs_bytes, z, count * 32)))) {
+        set_error(w + ": an output overlaps an input");
+        return BBG_E_INVALID;
+    }
+    if (proofs && ranges_overlap(proofs, proofs_bytes, y, y_bytes)) { set_error(w + ": the two outputs overlap"); return BBG_E_INVALID; }
+    return BBG_OK;
+}
 
 // ---------------------------------------------------------------------------------------------- divide by Z*_H
 __device__ Fr fr_inv_fermat(Fr a) { return fe_inverse_gcd(a); } // (the name is history: field.hip.h's binary extended Euclid since r4)

@@ -541,6 +541,78 @@ int bbg_poly_evaluate_lagrange(bbg_ctx* ctx, const uint64_t* evals, unsigned log
  * anything is queued, d_dest untouched.  Synchronous. */
 int bbg_kate_opening_lagrange_device(bbg_ctx* ctx, const void* d_evals, void* d_dest, unsigned log2n, const uint64_t z[4], uint64_t f_out[4]);
 
+/* ---- many Lagrange-form polynomials opened in ONE call, each at its OWN point (csrc/open_points.hip): the
+ *      compute_blob_kzg_proof of a blob library for a whole batch, and the last step of a PLONK prover.  d_evals holds `count` polynomials of
+ *      n = 2^log2n values each, contiguous and polynomial-major; d_z holds `count` points ON THE DEVICE (a Fiat-Shamir point computed there
+ *      never visits the host; z_k^n is log2n squarings in a kernel).  For every k < count
+ *          y[k]      = F_k(z_k)
+ *          proofs[k] = [ (F_k(X) - y_k) / (X - z_k) ]  committed over `lagrange`
+ *      `lagrange` must be a string in LAGRANGE form, which is what bbg_srs_lagrange returns; the call cannot tell whether it is, and over
+ *      any other string the proofs are commitments to something else.  Conventions of the Lagrange-form calls above: Montgomery Fr, every
+ *      input any representative in [0, 2r), y canonical; the proofs canonical affine, a proof at infinity (a constant polynomial) written
+ *      exactly as bbg_g1_ntt writes it.  d_proofs == NULL asks for the values only: `lagrange` may then be NULL, and no quotient and no MSM
+ *      is queued -- the y_k = F_k(z_k) step of a batch verifier.
+ *        A point ON the domain, z_k = w^m, is answered exactly, per polynomial (a batch may mix such polynomials with others): y_k = f_m, and
+ *      the quotient's value at w^m follows from the vanishing top coefficient of the quotient, q_m = - w^-m sum_(i != m) (f_m - f_i) /
+ *      (z w^-i - 1); no derivative is taken.  (bbg_kate_opening_lagrange_device keeps its documented refusal.)
+ *        1 <= log2n <= 28, 1 <= count <= 2^20.  BBG_E_INVALID with nothing queued and the outputs untouched: a null pointer other than the
+ *      two optional ones, log2n or count out of range, a string shorter than n or on another device than the context, an output that
+ *      overlaps an input or the other output.  The device form queues on the context stream only and does not synchronise the host once
+ *      the working memory has its size.  One launch per stage covers ALL polynomials of a chunk; the commitments go through the batched MSM,
+ *      BBG_MSM_BATCH_MAX polynomials per launch set.
+ *        Working memory: a chunk of c polynomials takes c (32 n + 64 ceil(n / 1024) + 160) bytes with proofs -- the quotient values, two
+ *      partial sums per inversion group of 1024 points, a slot for q_m, the MSM's Jacobian result, a flag -- and c (64 ceil(n / 1024) + 160)
+ *      without; it is counted under `scratch` in bbg_memory_report, released by bbg_memory_trim, and only grows.  c is what fits the budget
+ *      (1 GiB; bbg_open_points_set_budget), rounded down to a multiple of BBG_MSM_BATCH_MAX (at least one polynomial), and at most count;
+ *      a call with more polynomials walks them in chunks of c.  Beside it: the domain's constants and the MSM's arena.
+ *      Timed under "open_points_weights" (weights, partial sums, values), "open_points_quotient", "open_points_normalize" and the MSM's
+ *      names. ---- */
+int bbg_open_points_device(bbg_ctx* ctx, bbg_srs* lagrange, unsigned log2n, const void* d_evals /* count x n Fr */, const void* d_z /* count Fr, DEVICE */,
+                           size_t count, void* d_y /* count Fr */, void* d_proofs /* count x 64 B, or NULL */);
+/* Host-buffer form: upload, compute, download; synchronous.  proofs may be NULL (and `lagrange` then too). */
+int bbg_open_points(bbg_ctx* ctx, bbg_srs* lagrange, unsigned log2n, const uint64_t* evals, const uint64_t* z, size_t count, uint64_t* y, uint64_t* proofs);
+/* The bytes a chunk's working memory may take from the next call on (0 = the default, 1 GiB; at most 2^36).  A smaller budget means more,
+ * smaller chunks and the same results; memory already held is kept until bbg_memory_trim. */
+int bbg_open_points_set_budget(bbg_ctx* ctx, size_t bytes);
+
+/* ---- a batch of openings at ARBITRARY points reduced to ONE pairing check (csrc/kzg_verify.hip): the
+ *      verify_blob_kzg_proof_batch of a blob library, the last step of a batch of PLONK verifiers.  Opening i < N is a commitment C_i, a
+ *      point z_i, a claimed value y_i and a proof pi_i (what bbg_open_points writes).  With rho the caller's challenge and G = (1, 2)
+ *          L = sum_i rho^i pi_i
+ *          R = sum_i rho^i ( C_i - [y_i] G + [z_i] pi_i )
+ *      and over a powers string every opening is valid iff (with overwhelming probability over rho) e(L, [x]_2) = e(R, [1]_2).  No SRS takes
+ *      part.  One commitment per opening: repeating a commitment (one polynomial at several points) is legal, and so is repeating a point.
+ *      rho must be unpredictable to whoever made the proofs; rho^0 = 1 also for rho = 0.
+ *        Conventions, the curve check, the meaning of *d_off_curve and of the status word, and infinity as data are bbg_cells_verify_reduce's
+ *      and bbg_cells_verify's (above): Montgomery Fr in [0, 2r), points 64-byte Montgomery affine in [0, 2p) per coordinate, L then R
+ *      canonical affine with infinity as bbg_g1_ntt writes it; every finite commitment and proof is tested against y^2 = x^3 + 3 as it is
+ *      loaded, the number that fail goes to *d_off_curve (uint32, may be NULL), and L and R are then unspecified.  The host form returns
+ *      BBG_E_INVALID for a non-zero count and leaves `out` untouched.
+ *        1 <= N <= 2^27.  BBG_E_INVALID with nothing queued and the outputs untouched: a null pointer (d_off_curve excepted), N out of
+ *      range, an output that overlaps an input or the other output.  The device form queues on the context stream -- the powers of rho, one
+ *      kernel that packs the points [C | pi | G] and the scalars [rho^i | rho^i z_i | - sum rho^i y_i], and bbg_g1_msm_device's steps twice:
+ *      over the 2 N + 1 packed terms for R, over the proofs for L -- and does not synchronise the host once the working memory has its
+ *      size: 96 (2 N + 1) + 32 N + 128 KiB bytes of its own and the working memory of bbg_g1_msm (both `scratch` in bbg_memory_report,
+ *      released by bbg_memory_trim).  Timed under "kzg_verify_prepare" and bbg_g1_msm's names. ---- */
+int bbg_kzg_verify_reduce_device(bbg_ctx* ctx, const void* d_commitments /* N x 64 B */, const void* d_z, const void* d_y, const void* d_proofs, size_t N,
+                                 const uint64_t rho[4], void* d_out /* L, R */, void* d_off_curve /* uint32 or NULL */);
+/* Host-buffer form: upload, compute, download; synchronous. */
+int bbg_kzg_verify_reduce(bbg_ctx* ctx, const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t N,
+                          const uint64_t rho[4], uint64_t out[16]);
+/* The verdict in one call: the reduction above into the context's 512 bytes, then bbg_cells_verify_device's own last three steps ([L, -R]
+ * packed, bbg_pairing_product_wave_device at count 1, the status word), with no host round trip.  `lines`: a handle of exactly two points,
+ * ([x]_2, [1]_2) in that order.  *d_status (uint32): 1 every opening is valid under this rho, 0 not, 2 a finite commitment or proof is off
+ * the curve.  Calls may be queued back to back and read after one synchronisation, each writes its OWN d_status as its last step.
+ * BBG_E_INVALID with nothing queued and *d_status untouched: a null pointer, a handle with another pair count than two or made on another
+ * device, a status word that overlaps an input, and every refusal of the reduction.  Timed under the reduction's names, "cells_verify_pack"
+ * and "pairing_wave". */
+int bbg_kzg_verify_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d_commitments, const void* d_z, const void* d_y, const void* d_proofs, size_t N,
+                          const uint64_t rho[4], void* d_status);
+/* Host-buffer form: upload, the device form, download; synchronous.  Status 2 returns BBG_E_INVALID with *status written; every other
+ * error leaves it untouched. */
+int bbg_kzg_verify(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t N,
+                   const uint64_t rho[4], uint32_t* status);
+
 /* ---- device memory helpers for hosts that do not link HIP (bbmalloc/bbfree analogue, c_bind.cpp:11-15) ---- */
 int bbg_dev_alloc(bbg_ctx* ctx, size_t bytes, void** d_ptr);
 int bbg_dev_free(bbg_ctx* ctx, void* d_ptr);
@@ -704,7 +776,8 @@ typedef struct bbg_memory_info {
     size_t scratch;        /* NTT ping-pong buffer, host-entry staging, evaluation partials, widget constants, the fixed-base table, the
                               variable-base lanes' tables, the working set of bbg_g1_ntt, the tables of bbg_cells_recover,
                               the working set of bbg_cells_verify_reduce, the working memory of bbg_g1_msm and of bbg_pairing_product,
-                              the 512 bytes of bbg_cells_verify */
+                              the 512 bytes of bbg_cells_verify (and bbg_kzg_verify), the working sets of bbg_open_points and of
+                              bbg_kzg_verify_reduce */
     size_t prover_keys;    /* every live bbg_prover handle of this context (bbg_prover_device_bytes) */
     size_t total;          /* sum of the above */
     size_t device_total;   /* hipMemGetInfo: the device's memory ... */
