@@ -2,11 +2,11 @@
 // registry and the Ignition-transcript reader.  All arithmetic runs in the HIP kernels of ntt.hip / msm.hip.
 //
 // Most calls come as a *_device form on device pointers (the context lock, then the module) and a host-array twin, which reads: argument
-// checks, regions, upload, run, download.  Its regions are those of one Staged call (below): a StageLayout (stage_layout.h: offsets aligned
-// to 256 B, overflow reported) over ctx->staging, sized once; no entry point computes an offset into the staging buffer by hand.  The
-// checks several entry points word alike (log2n in a range, an SRS too short or on another device, a zero scalar) are bbg_internal.h's check_*.
+// checks, regions, upload, run, download.  Its regions are those of one Staged call (bbg_internal.h): a RegionLayout (region_layout.h: offsets
+// aligned to 256 B, overflow reported) over ctx->staging, sized once; no entry point computes an offset into the staging buffer by hand --
+// the two of pairing.hip, whose bodies live beside their kernels, included.  The checks several entry points word alike (log2n in a range,
+// an SRS too short or on another device, a zero scalar) are bbg_internal.h's check_*.
 #include "bbg_internal.h"
-#include "stage_layout.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -63,32 +63,7 @@ struct ScopedMem {
     }
 };
 
-// One staged call of a host-array entry point: a StageLayout bound to the context's staging buffer and stream.  The entry point asks for
-// its regions in order (each as large as the device call behind it may touch, slack included), ensure() sizes the buffer once -- a layout
-// that does not fit size_t is "<who>: size out of range" -- and st[region] is a pointer from then on; up() and down() queue the copies,
-// wait() ends the call.  Every step returns BBG_OK or the code of the HIP error with the text set.  The caller holds ctx->mu throughout.
-class Staged {
-  public:
-    struct Region { size_t off; };
-    Staged(bbg_ctx* c, const char* who_) : ctx(c), who(who_) {}
-    Region region(size_t bytes) { return { lay.add(bytes) }; }
-    Region region(size_t count, size_t each) { return { lay.add(count, each) }; }
-    int ensure()
-    {
-        if (!lay.ok()) { set_error(std::string(who) + ": size out of range"); return BBG_E_INVALID; }
-        return ctx->staging.ensure(lay.total());
-    }
-    char* operator[](Region r) const { return (char*)ctx->staging.p + r.off; }
-    int up(Region r, const void* host, size_t bytes) { BBG_HIP(hipMemcpyAsync((*this)[r], host, bytes, hipMemcpyHostToDevice, ctx->stream)); return BBG_OK; }
-    int down(void* host, Region r, size_t bytes) { BBG_HIP(hipMemcpyAsync(host, (*this)[r], bytes, hipMemcpyDeviceToHost, ctx->stream)); return BBG_OK; }
-    int wait() { BBG_HIP(hipStreamSynchronize(ctx->stream)); return BBG_OK; }
-
-  private:
-    bbg_ctx* ctx;
-    const char* who;
-    StageLayout lay;
-};
-// `step` is a Staged step or a module's run: leave the entry point with its code unless it is BBG_OK
+// `step` is a Staged step (bbg_internal.h) or a module's run: leave the entry point with its code unless it is BBG_OK
 #define BBG_TRY(step) do { if (int _rc = (step)) return _rc; } while (0)
 } // namespace
 
@@ -1356,14 +1331,14 @@ int bbg_g2_mul(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalar
 {
     CHECK_CTX(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return g2_mul_host(ctx, base_affine, scalars, n, out_affine, ctx->stream);
+    return g2_mul_host(ctx, base_affine, scalars, n, out_affine);
 }
 
 int bbg_g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, bbg_g2_lines** out)
 {
     CHECK_CTX(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return g2_lines_prepare(ctx, g2_affine, pairs, out, ctx->stream);
+    return g2_lines_prepare(ctx, g2_affine, pairs, out);
 }
 
 int bbg_g2_lines_pairs(const bbg_g2_lines* lines, size_t* pairs)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/bbg.h"
+#include "region_layout.h"
 
 namespace bbg {
 
@@ -70,6 +71,14 @@ struct DevBuf {
         bytes = 0;
     }
 };
+// `buf` with at least what a finished layout takes: BBG_E_INVALID with "<who>: size out of range" for one that does not fit size_t
+static inline int ensure_layout(DevBuf& buf, const RegionLayout& lay, const char* who)
+{
+    if (!lay.ok()) { set_error(std::string(who) + ": size out of range"); return BBG_E_INVALID; }
+    return buf.ensure(lay.total());
+}
+// the region at byte offset `off` of the buffer at `base`, as T
+template <class T> static inline T* at(void* base, size_t off) { return (T*)((char*)base + off); }
 
 // ---------------------------------------------------------------------------------------------- NTT
 constexpr int NTT_MAX_PASSES = 4;
@@ -291,6 +300,28 @@ struct ProfScope {
         if (stop) (void)hipEventRecord(stop, st);
     }
 };
+// One staged call of a host-array entry point: a RegionLayout (256 B regions) bound to the context's staging buffer and stream.  The entry
+// point asks for its regions in order (each as large as the device call behind it may touch, slack included), ensure() sizes the buffer
+// once -- a layout that does not fit size_t is "<who>: size out of range" -- and st[region] is a pointer from then on; up() and down() queue
+// the copies, wait() ends the call.  Every step returns BBG_OK or the code of the HIP error with the text set.  The caller holds ctx->mu
+// throughout.
+class Staged {
+  public:
+    struct Region { size_t off; };
+    Staged(bbg_ctx* c, const char* who_) : ctx(c), who(who_) {}
+    Region region(size_t bytes) { return { lay.add(bytes) }; }
+    Region region(size_t count, size_t each) { return { lay.add(count, each) }; }
+    int ensure() { return ensure_layout(ctx->staging, lay, who); }
+    char* operator[](Region r) const { return (char*)ctx->staging.p + r.off; }
+    int up(Region r, const void* host, size_t bytes) { BBG_HIP(hipMemcpyAsync((*this)[r], host, bytes, hipMemcpyHostToDevice, ctx->stream)); return BBG_OK; }
+    int down(void* host, Region r, size_t bytes) { BBG_HIP(hipMemcpyAsync(host, (*this)[r], bytes, hipMemcpyDeviceToHost, ctx->stream)); return BBG_OK; }
+    int wait() { BBG_HIP(hipStreamSynchronize(ctx->stream)); return BBG_OK; }
+
+  private:
+    bbg_ctx* ctx;
+    const char* who;
+    RegionLayout lay{ STAGE_ALIGN };
+};
 void msm_release_aux_streams(bbg_ctx* ctx); // bbg_capi.hip: destroys the reduce streams and their events, all handles null afterwards
 int ntt_run(bbg_ctx* ctx, void* d_coeffs, unsigned log2n, int op, size_t generator_size, const uint64_t* constant,
             hipStream_t stream);
@@ -400,10 +431,10 @@ int var_base_tables(bbg_ctx* ctx, size_t work, size_t* lanes, void** tables);
 int msm_points_run(bbg_ctx* ctx, const void* d_points, const void* d_scalars, size_t n, int window_bits, void* d_out, hipStream_t stream);
 // what such a call runs with (any out pointer may be null); needs no device
 int msm_points_plan(size_t n, int window_bits, int* c, int* windows, size_t* chunk_terms, size_t* segment_entries);
-// pairing.hip.  out_affine[i] = [scalars[i]] base on the twist: HOST arrays, base_affine NULL = the generator of G2; waits for `stream`.
-int g2_mul_host(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine, hipStream_t stream);
-// the lines of `pairs` finite points of the order-r subgroup of the twist (HOST, 128 B each); anything else is BBG_E_INVALID.  Waits for `stream`.
-int g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, struct bbg_g2_lines** out, hipStream_t stream);
+// pairing.hip.  out_affine[i] = [scalars[i]] base on the twist: HOST arrays, base_affine NULL = the generator of G2; a Staged call.
+int g2_mul_host(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine);
+// the lines of `pairs` finite points of the order-r subgroup of the twist (HOST, 128 B each); anything else is BBG_E_INVALID.  A Staged call.
+int g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, struct bbg_g2_lines** out);
 int g2_lines_read(const struct bbg_g2_lines* h, size_t which, uint64_t* out);
 void g2_lines_release(struct bbg_g2_lines* h);
 // the argument checks of bbg_pairing_product[_device] that look at no device memory: BBG_E_INVALID with the error text set

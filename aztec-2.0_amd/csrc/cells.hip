@@ -10,6 +10,7 @@
 //   A[i] = E[i] Zdom[i mod r]   ->   D = iNTT(A)   ->   B = cosetNTT(D),  B[i] /= Zcos[i mod r]   ->   f* = cosetiNTT(B).
 // This file: the kernels, their launches and the argument checks; the C ABI (bbg_capi.hip) holds the context lock and stages host arrays.
 #include "bbg_internal.h"
+#include "work_layouts.h"
 
 #include "ntt_consts.hip.h"
 
@@ -210,24 +211,25 @@ int cells_recover(bbg_ctx* ctx, const uint32_t* cell_ids, size_t K, const void* 
     if (ranges_overlap(d_values, count * K * l * 32, d_out_coeffs, count * n * 32)) { set_error(std::string(who) + ": the output overlaps the values"); return BBG_E_INVALID; }
     void* dc = nullptr;
     if (int rc = ntt_domain_consts(ctx, log2n, &dc)) return rc;
-    // the call's tables: roots (r) | points (2r) | Z (2r: Zcos, then Zdom by slot) | slot (r) | missing ids, then the known ids (r)
-    if (int rc = ctx->cells_work.ensure(r * (5 * 32 + 2 * 4))) return rc;
-    Fr* roots = (Fr*)ctx->cells_work.p;
-    Fr* pts = roots + r;
-    Fr* z = pts + 2 * r;
-    int32_t* slot = (int32_t*)(z + 2 * r);
-    uint32_t* lists = (uint32_t*)(slot + r);
+    // the call's tables: the regions of cr_layout (work_layouts.h)
+    const CrLayout L = cr_layout(r);
+    if (int rc = ensure_layout(ctx->cells_work, L.lay, who)) return rc;
+    void* ws = ctx->cells_work.p;
+    Fr *roots = at<Fr>(ws, L.roots), *pts = at<Fr>(ws, L.pts), *z = at<Fr>(ws, L.z);
+    void* d_in = at<void>(ws, L.in_at);
+    int32_t* slot = at<int32_t>(d_in, L.in.slot);
+    uint32_t* lists = at<uint32_t>(d_in, L.in.lists);
     // slot map and id lists, built in the context's pinned array (the copy below may run after this call has returned)
-    if (int rc = cells_pinned_ensure(ctx, r * 8)) return rc;
-    int32_t* h_slot = (int32_t*)ctx->cells_pinned;
-    uint32_t* h_lists = (uint32_t*)(h_slot + r);
+    if (int rc = cells_pinned_ensure(ctx, L.in.lay.total())) return rc;
+    int32_t* h_slot = at<int32_t>(ctx->cells_pinned, L.in.slot);
+    uint32_t* h_lists = at<uint32_t>(ctx->cells_pinned, L.in.lists);
     for (size_t m = 0; m < r; m++) h_slot[m] = -1;
     for (size_t k = 0; k < K; k++) h_slot[cell_ids[k]] = (int32_t)k;
     size_t q = 0;
     for (size_t m = 0; m < r; m++)
         if (h_slot[m] < 0) h_lists[q++] = (uint32_t)m;
     for (size_t k = 0; k < K; k++) h_lists[nm + k] = cell_ids[k];
-    BBG_HIP(hipMemcpyAsync(slot, ctx->cells_pinned, r * 8, hipMemcpyHostToDevice, st));
+    BBG_HIP(hipMemcpyAsync(d_in, ctx->cells_pinned, L.in.lay.total(), hipMemcpyHostToDevice, st));
     BBG_HIP(hipEventRecord(ctx->cells_copied, st));
     {
         ProfScope ps(ctx, "cells_z", st);

@@ -21,6 +21,7 @@
 //   * k_cv_phi           phi^m S_m by xyzz_mul_glv (an empty group is infinity and returns at once);
 //   * k_cv_reduce        the sums over m (and c) into at most CV_PARTS partial sums each, k_cv_finish the rest and the one inversion.
 #include "bbg_internal.h"
+#include "work_layouts.h"
 
 #include "curve.hip.h"
 #include "ntt_consts.hip.h"
@@ -232,34 +233,28 @@ int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log
     if (d_off_curve && ranges_overlap(d_off_curve, 4, d_out, 128)) { set_error(std::string(who) + ": the two outputs overlap"); return BBG_E_INVALID; }
     void* dc = nullptr;
     if (int rc = ntt_domain_consts(ctx, log2n, &dc)) return rc;
-    // working memory, all of it sized before the first launch: the lanes' tables, then
-    //   S (r) | Q (r), W_c C_c (ncom) | products (K) | partial sums (2 CV_PARTS) | [A] (96 B of 128) | E (n) | pw (K) | W (ncom) | counter | lists
+    // working memory, all of it sized before the first launch: the lanes' tables, then the regions of cv_layout (work_layouts.h)
     size_t lanes = 0;
     void* tables = nullptr;
     if (int rc = var_base_tables(ctx, std::max(K + ncom, r), &lanes, &tables)) return rc;
-    const size_t n_lists = (r + 1) + K + (ncom + 1) + K;
-    if (int rc = ctx->cells_work.ensure((2 * r + ncom + K + 2 * CV_PARTS + 1) * 128 + (n + K + ncom) * 32 + 16 + n_lists * 4)) return rc;
-    Xyzz* S = (Xyzz*)ctx->cells_work.p;
-    Xyzz* Q = S + r;
-    Xyzz* prod = Q + r + ncom;
-    Xyzz* parts = prod + K;
-    Jacobian* msm_a = (Jacobian*)(parts + 2 * CV_PARTS);
-    Fr* E = (Fr*)(parts + 2 * CV_PARTS + 1);
-    Fr* pw = E + n;
-    Fr* W = pw + K;
-    unsigned* bad = (unsigned*)(W + ncom);
-    uint32_t* lists = (uint32_t*)(bad + 4);
-    if (int rc = cells_pinned_ensure(ctx, n_lists * 4)) return rc;
-    uint32_t* h_off_m = (uint32_t*)ctx->cells_pinned;
-    uint32_t* h_perm_m = h_off_m + r + 1;
-    uint32_t* h_off_c = h_perm_m + K;
-    uint32_t* h_perm_c = h_off_c + ncom + 1;
-    cv_group(cell_ids, K, r, h_off_m, h_perm_m);
-    cv_group(commitment_ids, K, ncom, h_off_c, h_perm_c);
-    BBG_HIP(hipMemcpyAsync(lists, ctx->cells_pinned, n_lists * 4, hipMemcpyHostToDevice, st));
+    const CvLayout L = cv_layout(n, r, K, ncom, CV_PARTS);
+    if (int rc = ensure_layout(ctx->cells_work, L.lay, who)) return rc;
+    void* ws = ctx->cells_work.p;
+    Xyzz *S = at<Xyzz>(ws, L.S), *Q = at<Xyzz>(ws, L.Q), *prod = at<Xyzz>(ws, L.prod), *parts = at<Xyzz>(ws, L.parts);
+    Jacobian* msm_a = at<Jacobian>(ws, L.msm_a);
+    Fr *E = at<Fr>(ws, L.E), *pw = at<Fr>(ws, L.pw), *W = at<Fr>(ws, L.W);
+    unsigned* bad = at<unsigned>(ws, L.bad);
+    // the group lists: built in the pinned array, one copy, read from the same places of the device block
+    if (int rc = cells_pinned_ensure(ctx, L.in.lay.total())) return rc;
+    void* h_lists = ctx->cells_pinned;
+    cv_group(cell_ids, K, r, at<uint32_t>(h_lists, L.in.off_m), at<uint32_t>(h_lists, L.in.perm_m));
+    cv_group(commitment_ids, K, ncom, at<uint32_t>(h_lists, L.in.off_c), at<uint32_t>(h_lists, L.in.perm_c));
+    void* lists = at<void>(ws, L.lists);
+    BBG_HIP(hipMemcpyAsync(lists, h_lists, L.in.lay.total(), hipMemcpyHostToDevice, st));
     BBG_HIP(hipEventRecord(ctx->cells_copied, st));
     BBG_HIP(hipMemsetAsync(bad, 0, 4, st));
-    const uint32_t *off_m = lists, *perm_m = off_m + r + 1, *off_c = perm_m + K, *perm_c = off_c + ncom + 1;
+    const uint32_t *off_m = at<uint32_t>(lists, L.in.off_m), *perm_m = at<uint32_t>(lists, L.in.perm_m), *off_c = at<uint32_t>(lists, L.in.off_c),
+                   *perm_c = at<uint32_t>(lists, L.in.perm_c);
     {
         ProfScope ps(ctx, "cells_verify_powers", st);
         if (int rc = fixed_base_powers(rho, K, pw, st)) return rc;
@@ -280,7 +275,7 @@ int cells_verify_reduce(bbg_ctx* ctx, bbg_srs* srs, unsigned log2n, unsigned log
     {
         ProfScope ps(ctx, "cells_verify_mul", st);
         hipLaunchKernelGGL(k_cv_mul, dim3((unsigned)(lanes / 64)), dim3(64), 0, st, (const Affine*)d_proofs, (const Fr*)pw, perm_m, K, (const Affine*)d_commitments,
-                           (const Fr*)W, ncom, prod, Q + r, bad, (Xyzz*)tables);
+                           (const Fr*)W, ncom, prod, at<Xyzz>(ws, L.com_out), bad, (Xyzz*)tables);
     }
     {
         ProfScope ps(ctx, "cells_verify_segsum", st);

@@ -13,6 +13,7 @@
 //   * msm_points_run   over the pi with the rho^i (a window into the same arrays): L.
 // The verdict form runs cells_verify.hip's tail (cells_verdict_run: [L, -R] packed, the wave pairing at count 1, the status word).
 #include "bbg_internal.h"
+#include "work_layouts.h"
 
 #include "block_invert.hip.h"
 #include "curve.hip.h"
@@ -100,14 +101,14 @@ int kzg_verify_reduce(bbg_ctx* ctx, const void* d_commitments, const void* d_z, 
         return BBG_E_INVALID;
     }
     if (d_off_curve && ranges_overlap(d_off_curve, 4, d_out, 128)) { set_error(std::string(who) + ": the two outputs overlap"); return BBG_E_INVALID; }
-    // working memory, sized before the first launch: points (2N + 1) | scalars (2N + 1) | pw (N) | partial sums (KV_BLOCKS) | counter
+    // working memory, sized before the first launch: the regions of kv_layout (work_layouts.h)
     const size_t terms = 2 * N + 1;
-    if (int rc = ctx->kzg_work.ensure(terms * 64 + (terms + N + KV_BLOCKS) * 32 + 32)) return rc;
-    Affine* points = (Affine*)ctx->kzg_work.p;
-    Fr* scalars = (Fr*)(points + terms);
-    Fr* pw = scalars + terms;
-    Fr* partials = pw + N;
-    unsigned* bad = (unsigned*)(partials + KV_BLOCKS);
+    const KvLayout L = kv_layout(N, KV_BLOCKS);
+    if (int rc = ensure_layout(ctx->kzg_work, L.lay, who)) return rc;
+    void* ws = ctx->kzg_work.p;
+    Affine* points = at<Affine>(ws, L.points);
+    Fr *scalars = at<Fr>(ws, L.scalars), *pw = at<Fr>(ws, L.pw), *partials = at<Fr>(ws, L.partials);
+    unsigned* bad = at<unsigned>(ws, L.bad);
     const unsigned blocks = (unsigned)std::min<size_t>((N + 255) / 256, KV_BLOCKS);
     {
         ProfScope ps(ctx, "kzg_verify_prepare", st);

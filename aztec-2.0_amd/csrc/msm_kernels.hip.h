@@ -1077,9 +1077,8 @@ struct MsmLayout {
         off_cols[bbg_ctx::MSM_SLOTS], off_long[bbg_ctx::MSM_SLOTS], off_redo[bbg_ctx::MSM_SLOTS];
     size_t sort_bytes;
     size_t zero_bytes; // the leading part of the arena that holds the zero-initialised regions
-    size_t total;
+    RegionLayout lay{ 256 }; // every region rounded up to 256 B, the last included
 };
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Segment length (entries per accumulation lane).  Around 64 at the headline size; shorter for small MSMs, whose run time
 // is the latency of one lane's serial chain of mixed additions (64 additions = 0.43 ms regardless of n), and longer for
@@ -1129,28 +1128,26 @@ template <int C> static int msm_layout(size_t total_n, int sets, int cap_sets, b
     (void)library_sort;
 #endif
     L.sort_bytes = tmp;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-    L.off_parts = take((size_t)3 * cap_sets * SORT_PAD * 4); // per set: partition counts | bases | cursors (strides of cap_sets tables)
-    for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) L.off_redo[k] = take((size_t)2 * cap_sets * K::buckets * 4); // RedoQueue: flags (zero between MSMs), then the list
-    L.zero_bytes = o;
-    L.off_keys0 = take(L.entries * 4);
-    L.off_keys1 = take(L.entries * 4);
+    L.off_parts = L.lay.add((size_t)3 * cap_sets * SORT_PAD * 4); // per set: partition counts | bases | cursors (strides of cap_sets tables)
+    for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) L.off_redo[k] = L.lay.add((size_t)2 * cap_sets * K::buckets * 4); // RedoQueue: flags (zero between MSMs), then the list
+    L.off_keys0 = L.lay.add(L.entries * 4);
+    L.zero_bytes = L.off_keys0; // up to the first region behind them, their padding included
+    L.off_keys1 = L.lay.add(L.entries * 4);
     // sorted values, one copy per slot: a bucket queued for k_redo (reduce phase, auxiliary stream) is recomputed from its entries while the
     // next MSM already sorts
-    for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) L.off_vals0[k] = take(L.entries * 4);
-    L.off_vals1 = take(library_sort ? L.entries * 4 : 0); // second value buffer of the library sort's double buffer (A/B build only)
-    L.off_sort = take(L.sort_bytes);
+    for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) L.off_vals0[k] = L.lay.add(L.entries * 4);
+    L.off_vals1 = L.lay.add(library_sort ? L.entries * 4 : 0); // second value buffer of the library sort's double buffer (A/B build only)
+    L.off_sort = L.lay.add(L.sort_bytes);
     for (int k = 0; k < bbg_ctx::MSM_SLOTS; k++) {
-        L.off_offsets[k] = take((nbuckets + 2) * 4);
-        L.off_head[k] = take(L.lanes * sizeof(Xyzz));
-        L.off_tail[k] = take(L.lanes * sizeof(Xyzz));
-        L.off_buckets[k] = take(nbuckets * sizeof(Xyzz));
-        L.off_rows[k] = take((size_t)sets * ((size_t)(1 << K::log_rows) + MSM_MAX_PLANES) * sizeof(Xyzz)); // row sums of every set, then their bit planes
-        L.off_cols[k] = take((size_t)sets * (size_t)(1 << K::log_cols) * sizeof(Xyzz));
-        L.off_long[k] = take((nbuckets + 2) * 4); // long-bucket count, redo count, long-bucket list
+        L.off_offsets[k] = L.lay.add((nbuckets + 2) * 4);
+        L.off_head[k] = L.lay.add(L.lanes * sizeof(Xyzz));
+        L.off_tail[k] = L.lay.add(L.lanes * sizeof(Xyzz));
+        L.off_buckets[k] = L.lay.add(nbuckets * sizeof(Xyzz));
+        L.off_rows[k] = L.lay.add((size_t)sets * ((size_t)(1 << K::log_rows) + MSM_MAX_PLANES) * sizeof(Xyzz)); // row sums of every set, then their bit planes
+        L.off_cols[k] = L.lay.add((size_t)sets * (size_t)(1 << K::log_cols) * sizeof(Xyzz));
+        L.off_long[k] = L.lay.add((nbuckets + 2) * 4); // long-bucket count, redo count, long-bucket list
     }
-    L.total = o;
+    L.lay.close();
     return BBG_OK;
 }
 
@@ -1224,7 +1221,7 @@ int msm_run_c(bbg_ctx* ctx, const Srs& srs, const void* table_v, int sets, const
         ~ZeroRecordGuard() { if (!done) c->msm_zero_buf = nullptr; }
     } zero_guard{ctx};
     const size_t arena_had = ctx->msm.bytes;
-    rc = ctx->msm.ensure(L.total);
+    rc = ensure_layout(ctx->msm, L.lay, "bbg_msm");
     if (rc) return rc;
     if (ctx->msm.bytes != arena_had) ctx->msm_zero_buf = nullptr;
     rc = msm_ensure_aux_streams(ctx);

@@ -22,95 +22,14 @@
 // Terms are walked in chunks of MpPlan::chunk_terms; the buckets persist across chunks (cleared once per call).  Everything is queued on
 // one stream; the host waits only where the workspace has to grow.
 #include "bbg_internal.h"
+#include "work_layouts.h"
 #include "var_base.hip.h"
 
 namespace bbg {
 
-constexpr int MP_C_MIN = 2, MP_C_MAX = 16;
-constexpr size_t MP_MAX_N = (size_t)1 << 28;
-constexpr size_t MP_BUDGET = (size_t)1 << 30;    // working memory of one call, as bbg_open_all_batch
-constexpr size_t MP_CHUNK_CAP = (size_t)1 << 20; // terms per chunk at most
-constexpr size_t MP_LANE_BUCKETS = 65536;        // from this many buckets a segment is one lane's, below it one wave's
-constexpr size_t MP_SEG_LANE = 256, MP_SEG_WAVE = 1024;
-constexpr int MP_GROUP_LOG = 5;                  // buckets per group of the reduction: 2^5 at most
+// the plan of a call (MpPlan, mp_plan) and the working memory of one chunk (MpLayout, mp_layout) are plain host code: work_layouts.h
 constexpr unsigned MP_GRID_MAX = 16384;          // blocks of one wave: 16 per SIMD
 constexpr uint32_t MP_SIGN = 0x80000000u, MP_TWIN = 0x40000000u, MP_TERM = 0x3fffffffu;
-
-struct MpPlan {
-    int c = 0, windows = 0;
-    size_t chunk_terms = 0, segment_entries = 0;
-    bool lane = false;
-    size_t buckets = 0;        // windows 2^(c-1); the dump key
-    int group_log = 0;         // L = 2^group_log buckets per group
-    size_t groups = 0;         // per window
-    int lane_groups_log = 0;   // M = 2^lane_groups_log groups per lane of k_mp_reduce2
-};
-
-// the working memory of one chunk of T terms, in bytes (bbg.h): the regions of MpLayout in order
-struct MpLayout {
-    size_t buckets, sg, tg, winsum, partial, counts, off, cursor, segoff, entries, sorted, total;
-};
-
-static int mp_windows(int c) { return (128 + c - 1) / c; }
-
-// The automatic width: the fastest width of a sweep over every width at n = 2^8 .. 2^22 on an MI355X.  The cost model
-// 2 n windows(c) + 4 windows(c) 2^(c-1) it replaced asked for wider windows below 2^18 terms than the fixed tail of the reduction pays for.
-static int mp_auto_width(size_t n)
-{
-    if (n <= ((size_t)1 << 12)) return 4;
-    if (n <= ((size_t)1 << 15)) return 8;
-    if (n <= ((size_t)1 << 17)) return 9;
-    return 16;
-}
-
-static size_t mp_max_segments(const MpPlan& p, size_t T)
-{
-    const size_t entries = 2 * (size_t)p.windows * T;
-    return std::min(p.buckets, entries) + entries / p.segment_entries;
-}
-
-static MpLayout mp_layout(const MpPlan& p, size_t T)
-{
-    const size_t entries = 2 * (size_t)p.windows * T, bins = p.buckets + 1;
-    MpLayout l;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 127) / 128 * 128; return o; };
-    l.buckets = take(p.buckets * 128);
-    l.sg = take((size_t)p.windows * p.groups * 128);
-    l.tg = take((size_t)p.windows * p.groups * 128);
-    l.winsum = take((size_t)p.windows * 128);
-    l.partial = take(mp_max_segments(p, T) * 128);
-    l.counts = take(bins * 4);
-    l.off = take((bins + 1) * 4);
-    l.cursor = take(bins * 4);
-    l.segoff = take(bins * 4);
-    l.entries = take(entries * 4);
-    l.sorted = take(entries * 4);
-    l.total = at;
-    return l;
-}
-
-// false: window_bits is neither 0 nor a width of the range, or n is above the maximum
-static bool mp_plan(size_t n, int window_bits, MpPlan* out)
-{
-    if (n > MP_MAX_N) return false;
-    if (window_bits != 0 && (window_bits < MP_C_MIN || window_bits > MP_C_MAX)) return false;
-    MpPlan p;
-    p.c = window_bits ? window_bits : mp_auto_width(n);
-    p.windows = mp_windows(p.c);
-    p.buckets = (size_t)p.windows << (p.c - 1);
-    p.lane = p.buckets >= MP_LANE_BUCKETS;
-    p.segment_entries = p.lane ? MP_SEG_LANE : MP_SEG_WAVE;
-    p.group_log = std::min(p.c - 1, MP_GROUP_LOG);
-    p.groups = (size_t)1 << (p.c - 1 - p.group_log);
-    p.lane_groups_log = 0;
-    while (((size_t)64 << p.lane_groups_log) < p.groups) p.lane_groups_log++;
-    size_t T = MP_CHUNK_CAP;
-    while (mp_layout(p, T).total > MP_BUDGET) T -= T / 16; // a pure function of c: the first T of this sequence that fits
-    p.chunk_terms = T;
-    *out = p;
-    return true;
-}
 
 // ---------------------------------------------------------------------------------------------- device side
 // *(counter + key) += the lanes of the wave that hold `key`, and this lane's place among them: the value the counter had plus the lane's
@@ -394,7 +313,7 @@ int msm_points_run(bbg_ctx* ctx, const void* d_points, const void* d_scalars, si
     }
     const size_t T = std::max<size_t>(std::min(n, p.chunk_terms), 1);
     const MpLayout l = mp_layout(p, T);
-    if (int rc = ctx->msm_points_work.ensure(l.total)) return rc;
+    if (int rc = ensure_layout(ctx->msm_points_work, l.lay, who)) return rc;
     char* ws = (char*)ctx->msm_points_work.p;
     Xyzz *bucket_sums = (Xyzz*)(ws + l.buckets), *sg = (Xyzz*)(ws + l.sg), *tg = (Xyzz*)(ws + l.tg), *winsum = (Xyzz*)(ws + l.winsum), *partial = (Xyzz*)(ws + l.partial);
     uint32_t *counts = (uint32_t*)(ws + l.counts), *off = (uint32_t*)(ws + l.off), *cursor = (uint32_t*)(ws + l.cursor), *segoff = (uint32_t*)(ws + l.segoff);

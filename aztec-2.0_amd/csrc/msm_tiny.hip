@@ -23,6 +23,7 @@
 // Results are the same group elements as the bucket pipeline's (tests: every golden and oracle case at the sizes this path takes, batches,
 // ragged n, `from`, all-equal scalars, points at infinity, P and -P).  Selected by msm_auto_window (msm.hip) as window width 8.
 #include "msm_kernels.hip.h"
+#include "work_layouts.h"
 
 namespace bbg {
 
@@ -223,12 +224,11 @@ int msm_run_tiny(bbg_ctx* ctx, const Srs& srs, const void* table, int sets, cons
     if (max_n > ((size_t)1 << 20)) { set_error("msm_run_tiny: 8-bit windows are for small MSMs (n <= 2^20)"); return BBG_E_INVALID; }
     const uint32_t n_pad = (uint32_t)((max_n + 15) & ~(size_t)15);
     const uint32_t S = tiny_slices(max_n, sets);
-    const size_t mags_bytes = align_up((size_t)sets * T_WINDOWS * n_pad, 256), signs_bytes = align_up((size_t)sets * n_pad * 4, 256);
-    const size_t parts_bytes = align_up((size_t)sets * T_BUCKETS * S * sizeof(Xyzz), 256); // per reduce slot
+    const auto L = tiny_layout<bbg_ctx::MSM_SLOTS>((size_t)sets, n_pad, S, T_WINDOWS, T_BUCKETS); // work_layouts.h
     int rc = msm_ensure_aux_streams(ctx);
     if (rc) return rc;
     // (a growing buffer is released with hipFree, which waits for whatever still reads it)
-    rc = ctx->msm_tiny.ensure(mags_bytes + signs_bytes + bbg_ctx::MSM_SLOTS * parts_bytes);
+    rc = ensure_layout(ctx->msm_tiny, L.lay, "msm_run_tiny");
     if (rc) return rc;
     // The last kernel -- one block per MSM: the chip is idle beside it -- runs on this call's reduce stream like the bucket pipeline's reduce
     // phase (msm_async_reduce; bbg_join / msm_join wait for it), so that the NEXT MSM's recode and bucket kernels run beside it; the
@@ -244,9 +244,9 @@ int msm_run_tiny(bbg_ctx* ctx, const Srs& srs, const void* table, int sets, cons
         ctx->msm_tiny_layout = layout;
     }
     if (ctx->ev_done_valid[slot]) BBG_HIP(hipStreamWaitEvent(st, ctx->ev_done[slot], 0)); // this slot's bucket sums were last read two MSMs ago
-    uint8_t* mags = (uint8_t*)ctx->msm_tiny.p;
-    uint32_t* signs = (uint32_t*)(mags + mags_bytes);
-    Xyzz* parts = (Xyzz*)(mags + mags_bytes + signs_bytes + (size_t)slot * parts_bytes);
+    uint8_t* mags = at<uint8_t>(ctx->msm_tiny.p, L.mags);
+    uint32_t* signs = at<uint32_t>(ctx->msm_tiny.p, L.signs);
+    Xyzz* parts = at<Xyzz>(ctx->msm_tiny.p, L.parts[slot]); // per reduce slot
     if (h_scalars) BBG_HIP(hipMemcpyAsync((void*)d_scalars[0], h_scalars, n[0] * 32, hipMemcpyHostToDevice, st)); // bbg_msm: a batch of one
     {
         ProfScope ps(ctx, "msm_recode", st);

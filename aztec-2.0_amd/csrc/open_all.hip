@@ -38,6 +38,7 @@
 //   * the forward stages at r;
 //   * one normalisation, which writes a proof at infinity as aff_inf() (f of degree below l, for one).
 #include "bbg_internal.h"
+#include "work_layouts.h"
 #include "curve.hip.h"
 #include "ecntt.hip.h" // bit_reverse
 #include "ntt_consts.hip.h" // DomainConsts, pow_from_table
@@ -170,42 +171,32 @@ __global__ void __launch_bounds__(64) k_open_cells_sum(const Xyzz* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// The working arrays of a call, each for `cap` polynomials and polynomial-major, in ONE allocation: work2 | work1 | sum | c_hat.  The
-// handle's own workspace is this at cap = 1, the batched calls' at the reservation.
+// The working arrays of a call, each for `cap` polynomials and polynomial-major, in ONE allocation: oa_layout (work_layouts.h) bound to
+// its base.  The handle's own workspace is this at cap = 1, the batched calls' at the reservation.
 static_assert(sizeof(Xyzz) == 128 && sizeof(Fr) == 32, "the workspace is laid out in 128 B points and 32 B scalars");
 struct OpenAllWork {
-    Xyzz* work2; // cap x 2n: the 2n products of each polynomial
-    Xyzz* work1; // cap x r: the forward transforms' arrays
-    Xyzz* sum;   // cap x 2r, l >= 2 only: the summed products
-    Fr* c_hat;   // cap x 2n
-    Xyzz* inv;   // the inverse transforms' arrays: sum, or work2 for l = 1
+    Xyzz *work2, *work1, *sum;
+    Fr* c_hat;
+    Xyzz* inv; // the inverse transforms' arrays: sum, or work2 for l = 1
 };
 
 static OpenAllWork open_all_work(void* base, size_t cap, unsigned log2n, unsigned log2cell)
 {
-    const size_t m = (size_t)2 << log2n, proofs = (size_t)1 << (log2n - log2cell);
+    const OaLayout l = oa_layout(cap, log2n, log2cell);
     OpenAllWork w;
-    w.work2 = (Xyzz*)base;
-    w.work1 = w.work2 + cap * m;
-    w.sum = w.work1 + cap * proofs;
-    w.c_hat = (Fr*)(w.sum + (log2cell ? cap * 2 * proofs : 0));
+    w.work2 = at<Xyzz>(base, l.work2);
+    w.work1 = at<Xyzz>(base, l.work1);
+    w.sum = at<Xyzz>(base, l.sum);
+    w.c_hat = at<Fr>(base, l.c_hat);
     w.inv = log2cell ? w.sum : w.work2;
     return w;
 }
 
-// what the handle holds without a reservation: s_hat and the workspace of one polynomial
-size_t open_all_bytes(unsigned log2n, unsigned log2cell)
-{
-    const size_t n = (size_t)1 << log2n, r = n >> log2cell;
-    if (log2cell == 0) return 2 * n * 64 + 2 * n * 128 + n * 128 + 2 * n * 32;
-    return 2 * n * 64 + 2 * n * 128 + 2 * n * 32 + 2 * r * 128 + r * 128;
-}
-
 // the working arrays of one polynomial: what the handle holds beside s_hat
-size_t open_all_batch_poly_bytes(unsigned log2n, unsigned log2cell)
-{
-    return open_all_bytes(log2n, log2cell) - (((size_t)2 << log2n) * 64);
-}
+size_t open_all_batch_poly_bytes(unsigned log2n, unsigned log2cell) { return oa_layout(1, log2n, log2cell).lay.total(); }
+
+// what the handle holds without a reservation: s_hat (2n affine points) and the workspace of one polynomial
+size_t open_all_bytes(unsigned log2n, unsigned log2cell) { return ((size_t)2 << log2n) * 64 + open_all_batch_poly_bytes(log2n, log2cell); }
 
 void open_all_release(struct bbg_open_all* h)
 {
@@ -349,7 +340,9 @@ int open_all_batch_reserve(struct bbg_open_all* h, size_t polys)
         BBG_HIP(hipFree(old));
     }
     if (polys == 0) return BBG_OK;
-    hipError_t e = hipMalloc(&h->batch_ws, polys * open_all_batch_poly_bytes(h->log2n, h->log2cell));
+    const RegionLayout lay = oa_layout(polys, h->log2n, h->log2cell).lay;
+    if (!lay.ok()) { set_error("bbg_open_all_batch_reserve: size out of range"); return BBG_E_INVALID; }
+    hipError_t e = hipMalloc(&h->batch_ws, lay.total());
     if (e != hipSuccess) {
         h->batch_ws = nullptr;
         (void)hipGetLastError(); // the handle stays usable: a single call ends in a hipGetLastError of its own

@@ -19,6 +19,7 @@
 //   k_op_normalize  the chunk's results to canonical affine, four per thread behind one inversion (aff_batch_chunk4, curve.hip.h)
 // This file holds the kernels, the workspace and the chunk walk; the argument checks are poly.hip's (open_points_check).
 #include "bbg_internal.h"
+#include "work_layouts.h"
 
 #include "block_invert.hip.h"
 #include "curve.hip.h"
@@ -158,12 +159,8 @@ __global__ void __launch_bounds__(64) k_op_normalize(const Jacobian* __restrict_
     });
 }
 
-// the workspace of one chunk of `polys` polynomials: u | partials | hitq | Jacobian results | flags (bbg.h states the formula)
-size_t open_points_poly_bytes(unsigned log2n, bool proofs)
-{
-    const size_t n = (size_t)1 << log2n, groups = (n + BARY_BLK - 1) / BARY_BLK;
-    return (proofs ? 32 * n : 0) + 64 * groups + 160;
-}
+// the workspace of one polynomial: op_layout (work_layouts.h) at a chunk of one, which is the formula bbg.h states
+size_t open_points_poly_bytes(unsigned log2n, bool proofs) { return op_layout(log2n, proofs, 1, BARY_BLK).lay.total(); }
 size_t open_points_chunk(const bbg_ctx* ctx, unsigned log2n, bool proofs, size_t count)
 {
     size_t c = (size_t)ctx->open_points_budget / open_points_poly_bytes(log2n, proofs);
@@ -179,16 +176,18 @@ int open_points_run(bbg_ctx* ctx, bbg_srs* lagrange, unsigned log2n, const void*
     void* dc = nullptr;
     if (int rc = ntt_domain_consts(ctx, log2n, &dc)) return rc;
     const size_t chunk = open_points_chunk(ctx, log2n, proofs, count);
-    if (int rc = ctx->open_points_work.ensure(chunk * open_points_poly_bytes(log2n, proofs))) return rc;
+    const OpLayout L = op_layout(log2n, proofs, chunk, BARY_BLK);
+    if (int rc = ensure_layout(ctx->open_points_work, L.lay, "bbg_open_points_device")) return rc;
+    void* ws = ctx->open_points_work.p;
     OpArgs a;
     a.log2n = log2n;
     a.groups = (unsigned)groups;
     a.dc = (const DomainConsts*)dc;
-    a.u = proofs ? (Fr*)ctx->open_points_work.p : nullptr;
-    a.partials = (Fr*)ctx->open_points_work.p + (proofs ? chunk * n : 0);
-    a.hitq = a.partials + chunk * groups * 2;
-    Jacobian* jac = (Jacobian*)(a.hitq + chunk);
-    a.flag = (unsigned*)((char*)jac + chunk * 96);
+    a.u = proofs ? at<Fr>(ws, L.u) : nullptr;
+    a.partials = at<Fr>(ws, L.partials);
+    a.hitq = at<Fr>(ws, L.hitq);
+    Jacobian* jac = at<Jacobian>(ws, L.jac);
+    a.flag = at<unsigned>(ws, L.flag);
     for (size_t done = 0; done < count; done += chunk) {
         const size_t c = std::min(chunk, count - done);
         a.evals = (const Fr*)d_evals + done * n;

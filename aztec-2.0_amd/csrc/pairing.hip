@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "bbg_internal.h"
+#include "work_layouts.h"
 #include "curve.hip.h"
 #include "fq_tower.hip.h"
 
@@ -261,19 +262,19 @@ __global__ void __launch_bounds__(64, 1) k_pair_final(uint4* __restrict__ work, 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// the working memory of a call with `count` products: six lane-interleaved Fq12 slots and one flag word per product of a chunk
+// the products of one chunk of a call with `count` products, rounded up to whole waves: the stride of the lane-interleaved slots
 static size_t pair_stride(size_t count) { return (std::min(count, PAIR_CHUNK) + 63) / 64 * 64; }
-static size_t pair_work_bytes(size_t count) { return pair_stride(count) * ((size_t)PairP::FINAL_SLOTS * 384 + 4); }
 
-int g2_mul_host(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine, hipStream_t st)
+int g2_mul_host(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* out_affine)
 {
     const char* who = "bbg_g2_mul";
     if (n > G2_MUL_MAX) { set_error(std::string(who) + ": n is above 2^16"); return BBG_E_INVALID; }
     if (n && (!scalars || !out_affine)) { set_error(std::string(who) + ": null argument"); return BBG_E_INVALID; }
-    // base | flags (n + 1 words, the last for the base alone) | scalars | results
-    const size_t off_flags = 128, off_scalars = off_flags + (n + 1 + 31) / 32 * 128, off_out = off_scalars + n * 32 + 32;
-    if (int rc = ctx->staging.ensure(off_out + n * 128)) return rc;
-    char* d = (char*)ctx->staging.p;
+    Staged sg(ctx, who);
+    // flags: n + 1 words, the last for the base alone; scalars: the scalar 0 of the base's own check, then the caller's
+    const Staged::Region r_base = sg.region(128), r_flags = sg.region(n + 1, 4), r_scalars = sg.region(n + 1, 32), r_out = sg.region(n, 128);
+    if (int rc = sg.ensure()) return rc;
+    hipStream_t st = ctx->stream;
     uint64_t base[16];
     if (base_affine) memcpy(base, base_affine, 128);
     else {
@@ -283,55 +284,57 @@ int g2_mul_host(bbg_ctx* ctx, const uint64_t* base_affine, const uint64_t* scala
                 base[8 + 4 * h + w] = (uint64_t)PairP::G2_Y[h][2 * w] | ((uint64_t)PairP::G2_Y[h][2 * w + 1] << 32);
             }
     }
-    BBG_HIP(hipMemcpyAsync(d, base, 128, hipMemcpyHostToDevice, st));
-    BBG_HIP(hipMemsetAsync(d + off_scalars, 0, 32, st)); // the scalar 0 of the base's own check
-    if (n) BBG_HIP(hipMemcpyAsync(d + off_scalars + 32, scalars, n * 32, hipMemcpyHostToDevice, st));
+    const G2Aff* d_base = (const G2Aff*)sg[r_base];
+    Fr* d_scalars = (Fr*)sg[r_scalars];
+    uint32_t* d_flags = (uint32_t*)sg[r_flags];
+    if (int rc = sg.up(r_base, base, 128)) return rc;
+    BBG_HIP(hipMemsetAsync(d_scalars, 0, 32, st));
+    if (n) BBG_HIP(hipMemcpyAsync(d_scalars + 1, scalars, n * 32, hipMemcpyHostToDevice, st));
     // the base alone first (n = 0 validates it as well), then the products
-    hipLaunchKernelGGL(k_g2_mul, dim3(1), dim3(64), 0, st, (const G2Aff*)d, (size_t)0, (const Fr*)(d + off_scalars), (size_t)0, 1, (size_t)1, (G2Aff*)nullptr,
-                       (uint32_t*)(d + off_flags) + n);
+    hipLaunchKernelGGL(k_g2_mul, dim3(1), dim3(64), 0, st, d_base, (size_t)0, (const Fr*)d_scalars, (size_t)0, 1, (size_t)1, (G2Aff*)nullptr, d_flags + n);
     if (n)
-        hipLaunchKernelGGL(k_g2_mul, dim3(grid_for(n, 64)), dim3(64), 0, st, (const G2Aff*)d, (size_t)0, (const Fr*)(d + off_scalars + 32), (size_t)1, 0, n,
-                           (G2Aff*)(d + off_out), (uint32_t*)(d + off_flags));
+        hipLaunchKernelGGL(k_g2_mul, dim3(grid_for(n, 64)), dim3(64), 0, st, d_base, (size_t)0, (const Fr*)(d_scalars + 1), (size_t)1, 0, n, (G2Aff*)sg[r_out], d_flags);
     BBG_HIP(hipGetLastError());
     uint32_t flag = 0;
-    BBG_HIP(hipMemcpyAsync(&flag, (uint32_t*)(d + off_flags) + n, 4, hipMemcpyDeviceToHost, st));
-    BBG_HIP(hipStreamSynchronize(st));
+    BBG_HIP(hipMemcpyAsync(&flag, d_flags + n, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = sg.wait()) return rc;
     if (flag & G2_OFF_TWIST) { set_error(std::string(who) + ": the base point is not on the twist y^2 = x^3 + 3 / (9 + u)"); return BBG_E_INVALID; }
     if (n) {
-        BBG_HIP(hipMemcpyAsync(out_affine, d + off_out, n * 128, hipMemcpyDeviceToHost, st));
-        BBG_HIP(hipStreamSynchronize(st));
+        if (int rc = sg.down(out_affine, r_out, n * 128)) return rc;
+        if (int rc = sg.wait()) return rc;
     }
     return BBG_OK;
 }
 
-int g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, bbg_g2_lines** out, hipStream_t st)
+int g2_lines_prepare(bbg_ctx* ctx, const uint64_t* g2_affine, size_t pairs, bbg_g2_lines** out)
 {
     const char* who = "bbg_g2_lines_prepare";
     if (!g2_affine || !out) { set_error(std::string(who) + ": null argument"); return BBG_E_INVALID; }
     if (pairs < 1 || pairs > BBG_PAIRING_MAX_PAIRS) { set_error(std::string(who) + ": pairs must be 1 .. 8"); return BBG_E_INVALID; }
-    // points | the scalar r | flags
-    const size_t off_r = pairs * 128, off_flags = off_r + 32;
-    if (int rc = ctx->staging.ensure(off_flags + pairs * 4)) return rc;
-    char* d = (char*)ctx->staging.p;
+    Staged sg(ctx, who);
+    const Staged::Region r_points = sg.region(pairs, 128), r_r = sg.region(32), r_flags = sg.region(pairs, 4); // points | the scalar r | flags
+    if (int rc = sg.ensure()) return rc;
+    hipStream_t st = ctx->stream;
+    const G2Aff* d_points = (const G2Aff*)sg[r_points];
     void* d_lines = nullptr;
     BBG_HIP(hipMalloc(&d_lines, pairs * PAIR_LINES_BYTES));
     uint32_t flags[BBG_PAIRING_MAX_PAIRS];
-    hipError_t e = hipMemcpyAsync(d, g2_affine, pairs * 128, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + off_r, PairP::R_PLAIN, 32, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    int rc = sg.up(r_points, g2_affine, pairs * 128);
+    if (rc == BBG_OK) rc = sg.up(r_r, PairP::R_PLAIN, 32);
+    if (rc == BBG_OK) {
         ProfScope ps(ctx, "g2_lines", st);
         // [r] Q per point: finite, on the twist and of order r, or the handle is refused.  A lane of k_g2_lines that meets such a point computes
         // lines nobody reads.
-        hipLaunchKernelGGL(k_g2_mul, dim3(1), dim3(64), 0, st, (const G2Aff*)d, (size_t)1, (const Fr*)(d + off_r), (size_t)0, 1, pairs, (G2Aff*)nullptr,
-                           (uint32_t*)(d + off_flags));
-        hipLaunchKernelGGL(k_g2_lines, dim3(1), dim3(64), 0, st, (const G2Aff*)d, pairs, (char*)d_lines);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(k_g2_mul, dim3(1), dim3(64), 0, st, d_points, (size_t)1, (const Fr*)sg[r_r], (size_t)0, 1, pairs, (G2Aff*)nullptr, (uint32_t*)sg[r_flags]);
+        hipLaunchKernelGGL(k_g2_lines, dim3(1), dim3(64), 0, st, d_points, pairs, (char*)d_lines);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = hip_fail(e, who, __FILE__, __LINE__);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(flags, d + off_flags, pairs * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
+    if (rc == BBG_OK) rc = sg.down(flags, r_flags, pairs * 4);
+    if (rc == BBG_OK) rc = sg.wait();
+    if (rc != BBG_OK) {
         (void)hipFree(d_lines);
-        return hip_fail(e, who, __FILE__, __LINE__);
+        return rc;
     }
     for (size_t j = 0; j < pairs; j++) {
         const char* what = (flags[j] & G2_BASE_INF) ? "is the point at infinity" : (flags[j] & G2_OFF_TWIST) ? "is not on the twist y^2 = x^3 + 3 / (9 + u)"
@@ -385,10 +388,12 @@ int pairing_product_run(bbg_ctx* ctx, const bbg_g2_lines* h, const void* d_g1, s
         set_error(std::string(who) + ": an output overlaps the input or the other output");
         return BBG_E_INVALID;
     }
-    if (int rc = ctx->pairing_work.ensure(pair_work_bytes(count))) return rc;
+    // the working memory: pair_layout (work_layouts.h), six lane-interleaved Fq12 slots and one flag word per product of a chunk
     const size_t stride = pair_stride(count);
-    uint4* work = (uint4*)ctx->pairing_work.p;
-    uint32_t* flags = (uint32_t*)((char*)ctx->pairing_work.p + stride * (size_t)PairP::FINAL_SLOTS * 384);
+    const PairLayout L = pair_layout(stride, PairP::FINAL_SLOTS);
+    if (int rc = ensure_layout(ctx->pairing_work, L.lay, who)) return rc;
+    uint4* work = at<uint4>(ctx->pairing_work.p, L.work);
+    uint32_t* flags = at<uint32_t>(ctx->pairing_work.p, L.flags);
     for (size_t from = 0; from < count; from += PAIR_CHUNK) {
         const size_t n = std::min(count - from, PAIR_CHUNK);
         {

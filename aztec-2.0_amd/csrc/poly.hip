@@ -6,6 +6,7 @@
 //   divide_by_pseudo_vanishing_polynomial:628-725   pointwise division by Z*_H on the coset of the target domain
 // All results are the same field elements the reference computes (compared on canonical values).
 #include "bbg_internal.h"
+#include "work_layouts.h"
 
 #include <cstring>
 #include "ntt_consts.hip.h"
@@ -86,11 +87,11 @@ struct PolyHeader {
 };
 static int poly_scratch(bbg_ctx* ctx, size_t partials, PolyHeader** hdr, Fr** part)
 {
-    const size_t head = (sizeof(PolyHeader) + 255) / 256 * 256;
-    int rc = ctx->poly_scratch.ensure(head + (partials + 2) * sizeof(Fr));
+    const PolyLayout l = poly_layout(sizeof(PolyHeader), partials); // work_layouts.h
+    int rc = ensure_layout(ctx->poly_scratch, l.lay, "poly_scratch");
     if (rc) return rc;
-    *hdr = (PolyHeader*)ctx->poly_scratch.p;
-    if (part) *part = (Fr*)((char*)ctx->poly_scratch.p + head);
+    *hdr = at<PolyHeader>(ctx->poly_scratch.p, l.header);
+    if (part) *part = at<Fr>(ctx->poly_scratch.p, l.part);
     return BBG_OK;
 }
 

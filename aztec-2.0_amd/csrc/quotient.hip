@@ -14,6 +14,7 @@
 // One thread per domain point (the permutation kernel walks 4 consecutive points to amortise w^i).  All reads are
 // coalesced 32-byte elements: this is the one part of the prover that is genuinely HBM-streaming.
 #include "bbg_internal.h"
+#include "work_layouts.h"
 
 #include <cstring>
 #include <initializer_list>
@@ -661,10 +662,11 @@ static int gp_fill(bbg_ctx* ctx, int width, const void* const* d_wires, const vo
     a.n = (size_t)1 << log2n;
     a.block_rows = (size_t)256 * gp_rows_per_thread(a.n);
     a.nblocks = (a.n + a.block_rows - 1) / a.block_rows;
-    int rc = ctx->gp_totals.ensure((a.n + 2 * a.nblocks + 2) * sizeof(Fr));
+    const GpLayout l = gp_layout(a.n, a.nblocks); // work_layouts.h
+    int rc = ensure_layout(ctx->gp_totals, l.lay, "bbg_permutation_grand_product_device");
     if (rc) return rc;
-    a.sd = (Fr*)ctx->gp_totals.p;
-    a.bt = a.sd + a.n;
+    a.sd = at<Fr>(ctx->gp_totals.p, l.sd);
+    a.bt = at<Fr>(ctx->gp_totals.p, l.bt);
     a.z = (Fr*)d_z;
     QuotientSetup* setup = nullptr;
     rc = quot_setup_block(ctx, QUOT_SETUPS - 1, &setup); // its own block: the widgets' chain uses blocks 0 ..

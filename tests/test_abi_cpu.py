@@ -241,20 +241,29 @@ def test_shim_content_hash_host_logic(tmp_path, threads):
     assert outs[0] and outs[0] == outs[1], "the digest depends on the thread count"
 
 
-def test_stage_layout_host_logic(tmp_path):
-    """csrc/stage_layout.h -- the region arithmetic of every host-array entry point (bbg_capi.hip lays its staging buffer out with it) -- is
-    plain host C++: offsets ascending and multiples of 256, regions disjoint and as large as requested, the total the end of the last region,
-    zero-byte regions accepted, and a request or a sum that does not fit size_t reported instead of wrapped.  Built with g++ under the address
-    and undefined-behaviour sanitizers against the header alone (tests/tools/stage_layout_check.cpp has its own main) and run here as a
-    program of its own."""
+def test_region_layout_host_logic(tmp_path):
+    """csrc/region_layout.h -- the region arithmetic of every host-array entry point (bbg_capi.hip lays its staging buffer out with it) and of
+    the modules' device working memory (csrc/work_layouts.h) -- is plain host C++: offsets ascending and multiples of the layout's alignment
+    (packed, 4, 128, 256), regions disjoint and as large as requested, the total the end of the last region or, closed, that end rounded up,
+    zero-byte regions accepted, and a request or a sum that does not fit size_t reported instead of wrapped.  The modules' layout functions
+    are held, over a grid of shapes, to the closed forms include/bbg.h publishes and to their regions lying inside the total, disjoint and
+    aligned to their elements.  Built with g++ under the address and undefined-behaviour sanitizers against the two headers alone
+    (tests/tools/region_layout_check.cpp has its own main) and run here as a program of its own; the chunk_terms it prints for every window
+    width of bbg_g1_msm are those of tests/tools/msm_points_model.py."""
     import subprocess
-    exe = str(tmp_path / "stage_layout_check")
-    src = os.path.join(ROOT, "tests", "tools", "stage_layout_check.cpp")
+    import sys
+    exe = str(tmp_path / "region_layout_check")
+    src = os.path.join(ROOT, "tests", "tools", "region_layout_check.cpp")
     r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert r.returncode == 0, r.stdout.decode()
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    assert r.returncode == 0 and "stage_layout_check PASS" in r.stdout.decode(), r.stdout.decode()
+    out = r.stdout.decode()
+    assert r.returncode == 0 and "region_layout_check PASS" in out, out
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import msm_points_model as mp
+    printed = {int(ln.split()[1]): int(ln.split()[2]) for ln in out.splitlines() if ln.startswith("mp_chunk_terms ")}
+    assert printed == {c: mp.chunk_terms(c) for c in range(mp.C_MIN, mp.C_MAX + 1)}, printed
 
 
 def test_small_msm_final_stage_dataflow_model():

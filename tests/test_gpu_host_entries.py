@@ -1,6 +1,6 @@
 """The host-array entry points of the C ABI against their *_device twins, bit for bit.
 
-A host-array entry point stages its arrays through ONE device buffer of the context (csrc/bbg_capi.hip on csrc/stage_layout.h): it lays the
+A host-array entry point stages its arrays through ONE device buffer of the context (csrc/bbg_capi.hip on csrc/region_layout.h): it lays the
 buffer out in regions, uploads, runs the module's device call on the regions, downloads and waits.  Its twin takes device pointers and
 does the arithmetic alone, so the two must agree in every word whatever the inputs are; a wrong region offset, a region too small, a
 missing upload or download shows as a difference.  (The two MSMs over an SRS are compared in canonical affine form, every word of it:
