@@ -159,6 +159,8 @@ def load_library():
         "bbg_field_op": (cint, [vp, cint, cint, vp, vp, vp, sz]),
         "bbg_limb29_op": (cint, [vp, cint, cint, vp, sz, vp]),
         "bbg_limb29_op_shape": (cint, [cint, cint, ctypes.POINTER(cint), ctypes.POINTER(cint)]),
+        "bbg_tower_op": (cint, [vp, cint, vp, sz, vp]),
+        "bbg_tower_op_shape": (cint, [cint, ctypes.POINTER(cint), ctypes.POINTER(cint)]),
         "bbg_profile_enable": (cint, [vp, cint]),
         "bbg_profile_get": (cint, [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(sz)]),
         "bbg_prover_create": (cint, [vp, vp, ctypes.c_uint, cint, vp, ctypes.POINTER(vp)]),
@@ -203,7 +205,7 @@ EXPORTED_SYMBOLS = [
     "bbg_divide_by_pseudo_vanishing",
     "bbg_ntt_prepare", "bbg_coset_fft_split", "bbg_coset_fft_split_device", "bbg_scale_powers_device", "bbg_fr_root_pow", "bbg_fr_pow", "bbg_cross_dft_device", "bbg_poly_op_device", "bbg_poly_evaluate_device", "bbg_kate_opening_device",
     "bbg_divide_by_pseudo_vanishing_device", "bbg_dev_alloc", "bbg_dev_free",
-    "bbg_dev_upload", "bbg_dev_download", "bbg_set_option", "bbg_field_op", "bbg_limb29_op", "bbg_limb29_op_shape", "bbg_profile_enable", "bbg_profile_get",
+    "bbg_dev_upload", "bbg_dev_download", "bbg_set_option", "bbg_field_op", "bbg_limb29_op", "bbg_limb29_op_shape", "bbg_tower_op", "bbg_tower_op_shape", "bbg_profile_enable", "bbg_profile_get",
     "bbg_srs_write_transcript", "bbg_transcript_checksum", "bbg_srs_register_transcript_buffer",
     "bbg_prover_create", "bbg_prover_create_flavour", "bbg_prover_destroy", "bbg_prover_set_key_poly", "bbg_prover_finalize_key", "bbg_prover_round1", "bbg_prover_round3",
     "bbg_prover_round4", "bbg_prover_evaluate", "bbg_prover_linearise", "bbg_prover_round6", "bbg_prover_read_poly",
@@ -1014,4 +1016,21 @@ class Bbg:
             raise ValueError(f"expected (n, {operands}, 9) uint32 rows, got {rows.shape}")
         out = np.empty((rows.shape[0], results, 9), dtype=np.uint32)
         self._ck(self.lib.bbg_limb29_op(self.ctx, which, op, rows.ctypes.data, rows.shape[0], out.ctypes.data))
+        return out
+
+    def tower_op_shape(self, op):
+        """(operand rows, result rows) of a bbg_tower_op op; raises BbgError for an unknown op.  No device work."""
+        operands, results = ctypes.c_int(0), ctypes.c_int(0)
+        self._ck(self.lib.bbg_tower_op_shape(op, ctypes.byref(operands), ctypes.byref(results)))
+        return operands.value, results.value
+
+    def tower_op(self, op, rows):
+        """One device function of the pairing arithmetic on raw operands (bbg_tower_op): rows is (n, operands, 8) uint32, the result
+        (n, results, 8) uint32."""
+        operands, results = self.tower_op_shape(op)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if rows.ndim != 3 or rows.shape[1:] != (operands, 8):
+            raise ValueError(f"expected (n, {operands}, 8) uint32 rows, got {rows.shape}")
+        out = np.empty((rows.shape[0], results, 8), dtype=np.uint32)
+        self._ck(self.lib.bbg_tower_op(self.ctx, op, rows.ctypes.data, rows.shape[0], out.ctypes.data))
         return out

@@ -1781,4 +1781,30 @@ int bbg_limb29_op(bbg_ctx* ctx, int which, int op, const uint32_t* in, size_t n,
     return st.wait();
 }
 
+int bbg_tower_op_shape(int op, int* operands, int* results)
+{
+    if (!operands || !results) { set_error("bbg_tower_op_shape: null argument"); return BBG_E_INVALID; }
+    const int rc = tower_op_shape(op, operands, results);
+    if (rc) set_error("bbg_tower_op_shape: unknown op");
+    return rc;
+}
+int bbg_tower_op(bbg_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out)
+{
+    CHECK_CTX(ctx);
+    int operands = 0, results = 0;
+    if (tower_op_shape(op, &operands, &results)) { set_error("bbg_tower_op: unknown op"); return BBG_E_INVALID; }
+    if (n > ((size_t)1 << 16)) { set_error("bbg_tower_op: n > 2^16"); return BBG_E_INVALID; }
+    if (n == 0) return BBG_OK;
+    if (!in || !out) { set_error("bbg_tower_op: null argument"); return BBG_E_INVALID; }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const size_t in_bytes = n * operands * 32, out_bytes = n * results * 32; // rows of 8 words
+    Staged st(ctx, "bbg_tower_op");
+    const auto d_in = st.region(in_bytes), d_out = st.region(out_bytes), d_work = st.region(tower_op_work_bytes(op, n));
+    BBG_TRY(st.ensure());
+    BBG_TRY(st.up(d_in, in, in_bytes));
+    BBG_TRY(tower_op_device(op, st[d_in], st[d_out], st[d_work], n, ctx->stream));
+    BBG_TRY(st.down(out, d_out, out_bytes));
+    return st.wait();
+}
+
 } // extern "C"

@@ -387,6 +387,10 @@ int field_op_device(int which, int op, const void* a, const void* b, void* out, 
 // limb29_check.hip: the conformance kernels of the 29-bit-limb arithmetic (bbg_limb29_op)
 int limb29_op_shape(int which, int op, int* operands, int* results);
 int limb29_op_device(int which, int op, const void* d_in, void* d_out, size_t n, hipStream_t stream);
+// tower_check.hip: the conformance kernels of the pairing arithmetic (bbg_tower_op)
+int tower_op_shape(int op, int* operands, int* results);
+size_t tower_op_work_bytes(int op, size_t n);
+int tower_op_device(int op, const void* d_in, void* d_out, void* d_work, size_t n, hipStream_t stream);
 // h_scalars (optional): the n scalars are still on the HOST and d_scalars is where they belong on the device -- msm_run uploads them
 // itself, piece by piece, overlapped with its first pass
 int msm_run(bbg_ctx* ctx, Srs& srs, const void* d_scalars, size_t from, size_t n, void* d_out_jac,

@@ -100,6 +100,8 @@ template <class P> __device__ __forceinline__ uint32_t sub_limbs(uint32_t* r, co
 #define BBG_K8(A) A[0], A[1], A[2], A[3], A[4], A[5], A[6], A[7]
 
 // coarse add: inputs in [0,2p) -> output in [0,2p)   (field_impl_generic.hpp:196-234)
+// The closed interval is closed as well: for a, b in [0,2p] the sum is at most 4p < 2^256, one conditional subtraction of 2p (taken when
+// a + b >= 2p) leaves [0,2p], and the result is 2p only for a = b = 2p.  The extension tower (fq_tower.hip.h) relies on this.
 template <class P> __device__ __forceinline__ Fe<P> fe_add(const Fe<P>& a, const Fe<P>& b)
 {
     Fe<P> r = a;
@@ -108,6 +110,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_add(const Fe<P>& a, const
 }
 
 // coarse sub: inputs in [0,2p) -> output in [0,2p)   (field_impl_generic.hpp:254-271)
+// For a, b in [0,2p]: a - b where a >= b, else a - b + 2p < 2p, so the output is in [0,2p] and is 2p only for a = 2p, b = 0.
 template <class P> __device__ __forceinline__ Fe<P> fe_sub(const Fe<P>& a, const Fe<P>& b)
 {
     Fe<P> r = a;
@@ -139,7 +142,7 @@ template <class P> __device__ __forceinline__ Fe<P> fe_canon(const Fe<P>& a)
     return fe_reduce_once(fe_reduce_once(fe_reduce_once(a)));
 }
 
-// Montgomery product a*b*R^-1.  For inputs < 2p (even a < 4p with b < p) the result is < 2p
+// Montgomery product a*b*R^-1.  For inputs <= 2p (even a < 4p with b < p) the result is < 2p
 // with no final subtraction because 4p < 2^256 -- the same bound the reference relies on
 // (field_impl_generic.hpp:392-442 montgomery_mul, "coarse" form).
 //

@@ -1,7 +1,11 @@
 // The extension tower of BN254 for gfx950, on top of field.hip.h: Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - xi) with xi = 9 + u,
 // Fq12 = Fq6[w]/(w^2 - v) -- the reference's field2 / field6 / field12 (ecc/fields/field2.hpp, field6.hpp, field12.hpp) in its memory
-// layouts: fq2 = c0 | c1 (64 B), fq6 = c0 | c1 | c2, fq12 = c0 | c1 (384 B), Montgomery form.  Like Fq itself every coefficient is kept
-// coarsely reduced in [0, 2p] (fe_neg maps 0 to 2p) and canonicalised at the boundary (f2_canon, f12_store).  An Fq2 product is three
+// layouts: fq2 = c0 | c1 (64 B), fq6 = c0 | c1 | c2, fq12 = c0 | c1 (384 B), Montgomery form.  Every coefficient is kept coarsely reduced in
+// the CLOSED interval [0, 2p] (fe_neg maps 0 to 2p) and canonicalised at the boundary (f2_canon, f12_store).  field.hip.h states fe_add and
+// fe_sub for [0, 2p); both are closed on [0, 2p] too (the chains of addsub_chains.hip.h subtract 2p where a + b >= 2p and add it back on a
+// borrow: 2p + 2p -> 2p, 2p - 0 -> 2p, nothing above), fe_mul of operands <= 2p is below 2p, and fe_inverse_gcd canonicalises anything below
+// 4p.  What does NOT take the value 2p is a single fe_reduce_once (2p -> p) and with it fe_is_zero: zero tests here go through fq_canon, which
+// reduces twice.  tests/test_gpu_tower.py holds every function below to this contract on raw operands (bbg_tower_op).  An Fq2 product is three
 // Fq products (Karatsuba), an Fq6 product six Fq2 products, an Fq12 product three Fq6 products: 54 Fq products.  Constants:
 // pairing_consts.hip.h, generated from the integer model.
 #pragma once

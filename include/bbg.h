@@ -850,6 +850,16 @@ int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint6
  * BBG_E_INVALID (out untouched) for an unknown (which, op), a null pointer with n > 0, or n > 2^20; n = 0 is BBG_OK. */
 int bbg_limb29_op(bbg_ctx* ctx, int which, int op, const uint32_t* in, size_t n, uint32_t* out);
 int bbg_limb29_op_shape(int which, int op, int* operands, int* results);
+/* Self test entry of the pairing arithmetic, used by tests (like bbg_limb29_op: RAW operands, nothing is pre-reduced): one device function of
+ * csrc/fq_tower.hip.h, fq12_wave.hip.h or g2.hip.h per op, on coefficients anywhere in the tower's coarse range [0, 2p] -- a coefficient given
+ * as 2p arrives as 2p -- with the raw result words coming back.  in: n vectors of `operands` rows, out: n vectors of `results` rows
+ * (bbg_tower_op_shape gives both counts, without device work).  A row is one Fq value, 8 uint32_t, Montgomery form; an Fq2 is two rows
+ * (c0, c1), an Fq12 twelve in the reference's order; the ops of fq12_wave.hip.h take and return the twelve coefficients of a slot in the
+ * w-basis.  A boolean result is one row whose word 0 is 0 or 1 and whose other words are 0.  The op numbers are listed in
+ * csrc/tower_check.hip (BBG_TOWER_OPS).  The device checks no precondition: a coefficient above 2p gives wrapped arithmetic.
+ * BBG_E_INVALID (out untouched) for an unknown op, a null pointer with n > 0, or n > 2^16; n = 0 is BBG_OK. */
+int bbg_tower_op(bbg_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out);
+int bbg_tower_op_shape(int op, int* operands, int* results);
 
 #ifdef __cplusplus
 }

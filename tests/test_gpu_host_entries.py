@@ -13,9 +13,10 @@ test_gpu_var_base.py, test_gpu_fixed_base.py, test_gpu_barycentric.py, test_gpu_
   * large, small, large behind bbg_memory_trim: the staging buffer is allocated, reused while larger than needed, and grown
   * one invalid call per entry point with its return code and the exact text of bbg_last_error()
 
-The four entry points without a twin are held to the oracle by tests/test_gpu_g1_helpers.py::test_g1_normalize_mixed_entries
+The five entry points without a twin are held to the oracle by tests/test_gpu_g1_helpers.py::test_g1_normalize_mixed_entries
 (bbg_g1_normalize), tests/test_gpu_parity.py::test_field_ops (bbg_field_op), tests/test_gpu_limb29.py::test_device_primitive_against_its_model
-(bbg_limb29_op) and tests/test_gpu_coarse_range.py::test_coset_fft_split_and_extend_coarse (bbg_coset_fft_extend); here they run through the
+(bbg_limb29_op), tests/test_gpu_tower.py::test_device_function_against_the_model (bbg_tower_op, against the integer models) and
+tests/test_gpu_coarse_range.py::test_coset_fft_split_and_extend_coarse (bbg_coset_fft_extend); here they run through the
 large, small, large sequence against themselves (the same input gives the same output whatever the buffer held before) and the table."""
 import ctypes
 
@@ -330,6 +331,13 @@ def limb29_op(w, n):
     return w.bbg.limb29_op(0, 6, rows)
 
 
+def tower_op(w, n):
+    operands, results = w.bbg.tower_op_shape(0)  # f2_add: four rows in, two out
+    assert (operands, results) == (4, 2)
+    rows = (w.pkg.splitmix64_limbs(SEED + 51, n * operands * 8) & np.uint64((1 << 28) - 1)).astype(np.uint32).reshape(n, operands, 8)
+    return w.bbg.tower_op(0, rows)
+
+
 def coset_fft_extend(w, shape):
     lg, dom = shape
     return w.bbg.coset_fft_extend(scalars(w, 42, 1 << lg), dom)
@@ -339,6 +347,7 @@ NO_TWIN = {
     "bbg_g1_normalize": (g1_normalize, [3000, 1, 4000]),
     "bbg_field_op": (field_op, [3000, 1, 4000]),
     "bbg_limb29_op": (limb29_op, [3000, 1, 4000]),
+    "bbg_tower_op": (tower_op, [3000, 1, 4000]),
     "bbg_coset_fft_extend": (coset_fft_extend, [(8, 10), (1, 2), (9, 11)]),
 }
 
@@ -374,6 +383,7 @@ def test_zero_length_forms(world):
     a = scalars(w, 61, 1)
     assert lib.bbg_field_op(bbg.ctx, 0, 0, a.ctypes.data, None, out.ctypes.data, 0) == 0
     assert lib.bbg_limb29_op(bbg.ctx, 0, 0, None, 0, None) == 0
+    assert lib.bbg_tower_op(bbg.ctx, 0, None, 0, None) == 0
     assert np.array_equal(out, keep)
     assert lib.bbg_msm(bbg.ctx, w.srs.handle, None, 0, 0, out.ctypes.data) == 0 and lib.bbg_g1_sum(bbg.ctx, None, 0, out.ctypes.data) == 0
     assert lib.bbg_g1_msm(bbg.ctx, None, None, 0, 0, out.ctypes.data) == 0 and np.array_equal(out[:8], inf)
@@ -435,6 +445,8 @@ def test_invalid_calls_keep_their_code_and_text(world, pkg):
         (lambda: lib.bbg_field_op(ctx, 0, 0, None, None, p, 4), "bbg_field_op: null argument"),
         (lambda: lib.bbg_limb29_op(ctx, 0, 0, p, (1 << 20) + 1, p), "bbg_limb29_op: n > 2^20"),
         (lambda: lib.bbg_limb29_op(ctx, 0, 0, None, 4, p), "bbg_limb29_op: null argument"),
+        (lambda: lib.bbg_tower_op(ctx, 0, p, (1 << 16) + 1, p), "bbg_tower_op: n > 2^16"),
+        (lambda: lib.bbg_tower_op(ctx, 0, None, 4, p), "bbg_tower_op: null argument"),
         # the argument checks the constructors and handles share
         (lambda: lib.bbg_open_all_prepare(ctx, short.handle, 2, ctypes.byref(out_h)), "bbg_open_all_prepare: the SRS holds fewer than 2^log2n points"),
         (lambda: lib.bbg_open_all_prepare_cells(ctx, short.handle, 2, 1, ctypes.byref(out_h)), "bbg_open_all_prepare_cells: the SRS holds fewer than 2^log2n points"),
