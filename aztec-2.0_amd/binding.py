@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("BBG_LIB_PATH") or os.path.join(CSRC, "libbbg.so")  # 
 # op codes of bbg_ntt (include/bbg.h)
 FFT, IFFT, COSET_FFT, COSET_IFFT = 0, 1, 2, 3
 FFT_WITH_CONSTANT, COSET_FFT_WITH_CONSTANT, COSET_FFT_WITH_GENERATOR_SHIFT, IFFT_WITH_CONSTANT = 4, 5, 6, 7
+# forms of bbg_wire_decode / bbg_wire_encode (include/bbg.h)
+WIRE_G1_COMPRESSED, WIRE_G1_COMPRESSED_BYTES, WIRE_G1_BUFFER, WIRE_FR, WIRE_FR_BYTES = 0, 1, 2, 3, 4
 
 
 class BbgError(RuntimeError):
@@ -151,6 +153,11 @@ def load_library():
         "bbg_kzg_verify_reduce": (cint, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "bbg_kzg_verify_device": (cint, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
         "bbg_kzg_verify": (cint, [vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+        "bbg_wire_sizes": (cint, [cint, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "bbg_wire_decode_device": (cint, [vp, cint, vp, sz, vp, vp, vp]),
+        "bbg_wire_encode_device": (cint, [vp, cint, vp, sz, cint, vp, vp, vp]),
+        "bbg_wire_decode": (cint, [vp, cint, vp, sz, vp, vp, vp]),
+        "bbg_wire_encode": (cint, [vp, cint, vp, sz, cint, vp, vp, vp]),
         "bbg_dev_alloc": (cint, [vp, sz, ctypes.POINTER(vp)]),
         "bbg_dev_free": (cint, [vp, vp]),
         "bbg_dev_upload": (cint, [vp, vp, vp, sz]),
@@ -225,7 +232,16 @@ EXPORTED_SYMBOLS = [
     "bbg_pairing_product_device", "bbg_pairing_product", "bbg_pairing_product_wave_device", "bbg_pairing_product_wave",
     "bbg_open_points_device", "bbg_open_points", "bbg_open_points_set_budget",
     "bbg_kzg_verify_reduce_device", "bbg_kzg_verify_reduce", "bbg_kzg_verify_device", "bbg_kzg_verify",
+    "bbg_wire_sizes", "bbg_wire_decode_device", "bbg_wire_encode_device", "bbg_wire_decode", "bbg_wire_encode",
 ]
+
+
+def wire_sizes(form):
+    """(wire bytes, native bytes) per element of a form (bbg_wire_sizes: pure host, no context)."""
+    wb, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    if load_library().bbg_wire_sizes(form, ctypes.byref(wb), ctypes.byref(nb)) != 0:
+        raise BbgError(f"unknown wire form {form}")
+    return wb.value, nb.value
 
 
 class MemoryInfo(ctypes.Structure):
@@ -937,6 +953,45 @@ class Bbg:
         rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(4)
         self._ck(self.lib.bbg_kzg_verify_device(self.ctx, lines.handle, ctypes.c_void_p(d_commitments), ctypes.c_void_p(d_z), ctypes.c_void_p(d_y),
                                                 ctypes.c_void_p(d_proofs), N, rho.ctypes.data, ctypes.c_void_p(d_status)))
+
+    # ---- wire forms of G1 points and scalars (csrc/wire.hip)
+    def _wire_host(self, fn, form, src, n, out, extra, strict):
+        status = np.zeros(n, dtype=np.uint32)
+        bad = ctypes.c_uint32(0)
+        rc = fn(self.ctx, form, src.ctypes.data, n, *extra, out.ctypes.data, status.ctypes.data, ctypes.byref(bad))
+        if rc != 0 and (strict or bad.value == 0):  # a bad element returns BBG_E_INVALID behind the outputs; anything else left them untouched
+            self._ck(rc)
+        return out, status, int(bad.value)
+
+    def wire_decode(self, form, wire, strict=True):
+        """n wire elements (bytes, or any array of n x wire_sizes(form)[0] bytes) to (native, status, bad): native (n, 8) Montgomery affine or
+        (n, 4) Montgomery Fr words, status (n,) uint32 (1 valid, 3 infinity, 0 malformed, 2 not on the curve), bad the count of 0s and 2s.
+        strict: a bad element raises BbgError; strict=False returns what the call wrote (bbg_wire_decode)."""
+        wb, nb = wire_sizes(form)
+        src = np.frombuffer(wire, dtype=np.uint8) if isinstance(wire, (bytes, bytearray)) else np.ascontiguousarray(wire).view(np.uint8).reshape(-1)
+        if src.size % wb:
+            raise ValueError(f"expected a multiple of {wb} bytes, got {src.size}")
+        n = src.size // wb
+        return self._wire_host(self.lib.bbg_wire_decode, form, src, n, np.zeros((n, nb // 8), dtype=np.uint64), (), strict)
+
+    def wire_encode(self, form, native, check=1, strict=True):
+        """The inverse: native words to (wire, status, bad), wire an (n, wire_sizes(form)[0]) uint8 array.  check = 1 tests every finite point
+        against the curve (status 2, counted in bad, the form's infinity written) (bbg_wire_encode)."""
+        wb, nb = wire_sizes(form)
+        src = _u64(native, nb // 8)
+        n = src.shape[0]
+        return self._wire_host(self.lib.bbg_wire_encode, form, src, n, np.zeros((n, wb), dtype=np.uint8), (int(check),), strict)
+
+    def wire_decode_device(self, form, d_wire, n, d_native, d_status=None, d_bad=None):
+        """Device pointers (16-byte aligned data, n uint32 status words or None, one uint32 count or None); asynchronous on the context
+        stream (bbg_wire_decode_device)."""
+        self._ck(self.lib.bbg_wire_decode_device(self.ctx, form, ctypes.c_void_p(d_wire), n, ctypes.c_void_p(d_native),
+                                                 ctypes.c_void_p(d_status) if d_status else None, ctypes.c_void_p(d_bad) if d_bad else None))
+
+    def wire_encode_device(self, form, d_native, n, check, d_wire, d_status=None, d_bad=None):
+        """Device pointers as wire_decode_device; asynchronous on the context stream (bbg_wire_encode_device)."""
+        self._ck(self.lib.bbg_wire_encode_device(self.ctx, form, ctypes.c_void_p(d_native), n, int(check), ctypes.c_void_p(d_wire),
+                                                 ctypes.c_void_p(d_status) if d_status else None, ctypes.c_void_p(d_bad) if d_bad else None))
 
     # host-buffer forms (what the C++ shim binds evaluate / compute_kate_opening_coefficients / divide_by_pseudo_vanishing_polynomial to)
     def poly_evaluate(self, coeffs, z):

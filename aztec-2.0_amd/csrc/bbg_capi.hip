@@ -1717,6 +1717,68 @@ int bbg_kzg_verify(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* comm
     }
     return BBG_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ wire forms of G1 points and scalars (wire.hip)
+int bbg_wire_sizes(int form, size_t* wire_bytes, size_t* native_bytes)
+{
+    const int rc = wire_sizes(form, wire_bytes, native_bytes);
+    if (rc) set_error("bbg_wire_sizes: unknown form");
+    return rc;
+}
+
+int bbg_wire_decode_device(bbg_ctx* ctx, int form, const void* d_wire, size_t n, void* d_native, void* d_status, void* d_bad)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return wire_decode_run(ctx, "bbg_wire_decode_device", form, d_wire, n, d_native, d_status, d_bad, ctx->stream);
+}
+
+int bbg_wire_encode_device(bbg_ctx* ctx, int form, const void* d_native, size_t n, int check, void* d_wire, void* d_status, void* d_bad)
+{
+    CHECK_CTX(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return wire_encode_run(ctx, "bbg_wire_encode_device", form, d_native, n, check, d_wire, d_status, d_bad, ctx->stream);
+}
+
+// the host twin of both directions: `in` (in_each bytes per element) up, the device call, `out`, the status words and the count down
+static int wire_staged(bbg_ctx* ctx, const char* who, bool encode, int form, int check, const void* in, size_t n, void* out, uint32_t* status, uint32_t* bad)
+{
+    size_t wire_bytes = 0, native_bytes = 0;
+    (void)wire_sizes(form, &wire_bytes, &native_bytes); // an unknown form is wire_check's to report
+    const size_t in_each = encode ? native_bytes : wire_bytes, out_each = encode ? wire_bytes : native_bytes;
+    BBG_TRY(wire_check(who, form, check, n, in, in_each, out, out_each, status, bad)); // before the staging buffer is sized by n
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    Staged st(ctx, who);
+    const auto d_in = st.region(n, in_each), d_out = st.region(n, out_each), d_status = st.region(n, 4), d_bad = st.region(4);
+    BBG_TRY(st.ensure());
+    if (n) BBG_TRY(st.up(d_in, in, n * in_each));
+    if (encode) BBG_TRY(wire_encode_run(ctx, who, form, st[d_in], n, check, st[d_out], st[d_status], st[d_bad], ctx->stream));
+    else BBG_TRY(wire_decode_run(ctx, who, form, st[d_in], n, st[d_out], st[d_status], st[d_bad], ctx->stream));
+    uint32_t count = 0;
+    if (n) BBG_TRY(st.down(out, d_out, n * out_each));
+    if (n && status) BBG_TRY(st.down(status, d_status, n * 4));
+    BBG_TRY(st.down(&count, d_bad, 4));
+    BBG_TRY(st.wait());
+    if (bad) *bad = count;
+    if (count) {
+        set_error(std::string(who) + ": " + std::to_string(count) + " of the elements are malformed or not on the curve");
+        return BBG_E_INVALID;
+    }
+    return BBG_OK;
+}
+
+int bbg_wire_decode(bbg_ctx* ctx, int form, const void* wire, size_t n, void* native, uint32_t* status, uint32_t* bad)
+{
+    CHECK_CTX(ctx);
+    return wire_staged(ctx, "bbg_wire_decode", false, form, 0, wire, n, native, status, bad);
+}
+
+int bbg_wire_encode(bbg_ctx* ctx, int form, const void* native, size_t n, int check, void* wire, uint32_t* status, uint32_t* bad)
+{
+    CHECK_CTX(ctx);
+    return wire_staged(ctx, "bbg_wire_encode", true, form, check, native, n, wire, status, bad);
+}
+
 int bbg_divide_by_pseudo_vanishing(bbg_ctx* ctx, uint64_t* evals, unsigned log2_src, unsigned log2_target, size_t num_roots_cut)
 {
     CHECK_CTX(ctx);
@@ -1743,6 +1805,7 @@ int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint6
 {
     CHECK_CTX(ctx);
     if (!a || !out) { set_error("bbg_field_op: null argument"); return BBG_E_INVALID; }
+    if (op == 12 && which != 1) { set_error("bbg_field_op: op 12 is the square root of Fq only (which = 1)"); return BBG_E_INVALID; }
     if (n == 0) return BBG_OK;
     std::lock_guard<std::mutex> lk(ctx->mu);
     Staged st(ctx, "bbg_field_op");
@@ -1750,7 +1813,8 @@ int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint6
     BBG_TRY(st.ensure());
     BBG_TRY(st.up(d_a, a, n * 32));
     if (b) BBG_TRY(st.up(d_b, b, n * 32));
-    BBG_TRY(field_op_device(which, op, st[d_a], b ? st[d_b] : nullptr, st[d_out], n, ctx->stream));
+    if (op == 12) BBG_TRY(wire_sqrt_device(st[d_a], st[d_out], n, ctx->stream));
+    else BBG_TRY(field_op_device(which, op, st[d_a], b ? st[d_b] : nullptr, st[d_out], n, ctx->stream));
     BBG_TRY(st.down(out, d_out, n * 32));
     return st.wait();
 }

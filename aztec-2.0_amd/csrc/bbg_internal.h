@@ -511,4 +511,15 @@ int kzg_verify_reduce(bbg_ctx* ctx, const void* d_commitments, const void* d_z, 
 // *d_status as cells_verify_run writes it; `lines`: the handle of ([x]_2, [1]_2)
 int kzg_verify_run(bbg_ctx* ctx, const struct bbg_g2_lines* lines, const void* d_commitments, const void* d_z, const void* d_y, const void* d_proofs, size_t N,
                    const uint64_t* rho, void* d_status, hipStream_t stream);
+// wire.hip.  The bytes per element of a form (either pointer may be null); BBG_E_INVALID for an unknown form, no error text.
+int wire_sizes(int form, size_t* wire_bytes, size_t* native_bytes);
+// every refusal that looks at no alignment, on host or device pointers alike: BBG_E_INVALID with the error text set
+int wire_check(const char* who, int form, int check, size_t n, const void* in, size_t in_each, const void* out, size_t out_each, const void* status,
+               const void* bad);
+// the device calls: wire_check, the alignment of the device pointers, then the memset of *d_bad and one kernel.  Queue only.
+int wire_decode_run(bbg_ctx* ctx, const char* who, int form, const void* d_wire, size_t n, void* d_native, void* d_status, void* d_bad, hipStream_t stream);
+int wire_encode_run(bbg_ctx* ctx, const char* who, int form, const void* d_native, size_t n, int check, void* d_wire, void* d_status, void* d_bad,
+                    hipStream_t stream);
+// out[i] = a[i]^((q + 1) / 4) in Fq, canonical Montgomery (bbg_field_op, op 12)
+int wire_sqrt_device(const void* d_a, void* d_out, size_t n, hipStream_t stream);
 } // namespace bbg

@@ -613,6 +613,55 @@ int bbg_kzg_verify_device(bbg_ctx* ctx, const bbg_g2_lines* lines, const void* d
 int bbg_kzg_verify(bbg_ctx* ctx, const bbg_g2_lines* lines, const uint64_t* commitments, const uint64_t* z, const uint64_t* y, const uint64_t* proofs, size_t N,
                    const uint64_t rho[4], uint32_t* status);
 
+/* ---- wire forms: G1 points and scalars as they cross a network or sit in a proof, decoded to and encoded from the native form of every
+ *      other entry point, on the device (csrc/wire.hip).  Paths relative to barretenberg/src/aztec/.  q is the modulus of Fq,
+ *      r that of Fr.
+ *        Native side: exactly what the other calls take and give.  G1: 64-byte Montgomery affine x || y.  Decode writes canonical
+ *      coordinates and writes infinity as bbg_g1_ntt does (bit 63 of x.data[3] set, every other bit zero); encode accepts any representative in
+ *      [0, 2q) per coordinate and that infinity encoding as data.  Fr: 32-byte Montgomery; decode writes it canonical, encode accepts [0, 2r).
+ *        Compressed forms (32 B): for a finite point the word is, bit for bit, the reference's uint256_t(P) (affine_element::operator uint256_t,
+ *      ecc/groups/affine_element_impl.hpp:24-40, 58-65): canonical non-Montgomery x in bits 0 .. 253, bit 0 of canonical y in bit 255.  The
+ *      reference cannot express infinity in this form; here it is bit 254 set and every other bit zero (q < 2^254, so no finite word sets bit
+ *      254).  A word with bit 254 and any other bit set is malformed, and so is one whose x is not below q.  This is STRICTER than the
+ *      reference, whose constructor reduces x silently and returns a point that is not on the curve when x^3 + 3 is a non-residue: here the
+ *      first is status 0 and the second status 2.  y is recovered as (x^3 + 3)^((q + 1) / 4) and accepted iff its square is x^3 + 3.
+ *        Buffer form (64 B): y, then x, 32 bytes each, most significant byte first, canonical.  Decode: bit 7 of byte 0 set is the point at
+ *      infinity whatever the other 511 bits hold, as the reference reads it; otherwise bit 6 of byte 0 and both coordinates are range-checked
+ *      and the point is tested against y^2 = x^3 + 3.  Encode writes infinity as 0x80 followed by 63 zero bytes (the reference writes
+ *      unspecified bytes under the flag, and its reader ignores them).
+ *        Status word per element (d_status: n uint32, may be NULL); *d_bad (uint32, may be NULL) counts the statuses 0 and 2, is written by
+ *      every call and is 0 for n = 0:
+ *          1   finite and valid
+ *          3   the point at infinity (G1 forms only; valid)
+ *          0   malformed: a coordinate or scalar not below its modulus, or an undefined flag bit
+ *          2   well-formed but not on the curve: x^3 + 3 a non-residue (compressed forms), y^2 != x^3 + 3 (buffer form, encode with check)
+ *      An element with status 0 or 2 writes the infinity encoding (of the native side, or of the form) for G1 and zero for Fr, so calls
+ *      downstream see a defined value and nothing else is affected.
+ *        Encode: check = 1 tests every finite point against the curve (status 2, counted, the form's infinity written); check = 0 writes x
+ *      and the parity of whatever y it is given, status 1 or 3.  For the Fr forms check is ignored (but must be 0 or 1) and every status is 1.
+ *        n is at most 2^28; n = 0 is legal.  BBG_E_INVALID with nothing queued and every output untouched: a null context, a null data
+ *      pointer with n > 0, an unknown form, check other than 0 or 1, n out of range, any overlap between the input and the outputs or between
+ *      two outputs, and -- the device forms only, whose kernels move 16 bytes per access -- a data pointer that is not 16-byte aligned or a
+ *      status or count pointer that is not 4-byte aligned.  The device forms queue on the context stream only (a memset of *d_bad and one
+ *      kernel, one lane per element), use no working memory and never synchronise the host.  Timed under "wire_decode" and "wire_encode"
+ *      (bbg_profile_get). ---- */
+#define BBG_WIRE_G1_COMPRESSED       0  /* 32 B: the reference's in-memory uint256_t, 4 x u64 little-endian limbs */
+#define BBG_WIRE_G1_COMPRESSED_BYTES 1  /* the same word as 32 bytes, most significant first (write(buf, uint256_t), numeric/uint256/uint256.hpp:188-195) */
+#define BBG_WIRE_G1_BUFFER           2  /* 64 B: affine_element::serialize_to_buffer (ecc/groups/affine_element.hpp:38-56) */
+#define BBG_WIRE_FR                  3  /* 32 B: the canonical integer as 4 x u64 little-endian limbs (uint256_t(fr)) */
+#define BBG_WIRE_FR_BYTES            4  /* 32 B big-endian canonical: fr::serialize_to_buffer (ecc/fields/field.hpp:189-191) */
+/* Bytes per element on either side of a form (either pointer may be NULL); a pure host function that needs no device and no context.
+ * BBG_E_INVALID for an unknown form. */
+int bbg_wire_sizes(int form, size_t* wire_bytes, size_t* native_bytes);
+int bbg_wire_decode_device(bbg_ctx* ctx, int form, const void* d_wire, size_t n, void* d_native, void* d_status /* n uint32 or NULL */,
+                           void* d_bad /* uint32 or NULL */);
+int bbg_wire_encode_device(bbg_ctx* ctx, int form, const void* d_native, size_t n, int check, void* d_wire, void* d_status, void* d_bad);
+/* Host-buffer forms: upload, the device form, download; synchronous; no alignment is asked of host pointers.  A non-zero count of bad
+ * elements returns BBG_E_INVALID AFTER the outputs, the status words and *bad have been written, so the caller can see which elements
+ * they were (as bbg_pairing_product does for status 2); every other error leaves them untouched. */
+int bbg_wire_decode(bbg_ctx* ctx, int form, const void* wire, size_t n, void* native, uint32_t* status, uint32_t* bad);
+int bbg_wire_encode(bbg_ctx* ctx, int form, const void* native, size_t n, int check, void* wire, uint32_t* status, uint32_t* bad);
+
 /* ---- device memory helpers for hosts that do not link HIP (bbmalloc/bbfree analogue, c_bind.cpp:11-15) ---- */
 int bbg_dev_alloc(bbg_ctx* ctx, size_t bytes, void** d_ptr);
 int bbg_dev_free(bbg_ctx* ctx, void* d_ptr);
@@ -832,13 +881,15 @@ int bbg_set_option(bbg_ctx* ctx, const char* key, long value);
  * "fr_batch_invert", "barycentric", "open_all_prepare", "open_all_coeffs", "open_all_pointwise", "open_all_fold", "open_cells_sum",
  * "cells_gather", "cells_z", "cells_scatter", "cells_divide", "cells_canon", "cells_verify_powers", "cells_verify_fold", "cells_verify_mul",
  * "cells_verify_segsum", "cells_verify_phi", "cells_verify_finish", "msm_points_sort", "msm_points_accumulate", "msm_points_reduce",
- * "msm_points_combine", "g2_lines", "pairing_miller", "pairing_final".  enable(…, 1) clears previous samples. */
+ * "msm_points_combine", "g2_lines", "pairing_miller", "pairing_final", "wire_decode", "wire_encode".  enable(…, 1) clears previous samples. */
 int bbg_profile_enable(bbg_ctx* ctx, int on);
 int bbg_profile_get(bbg_ctx* ctx, const char* name, double* total_ms, size_t* launches);
 /* Field-level self test entry used by tests: out[i] = a[i] (op) b[i] computed by the device field code.
  * which: 0 Fr, 1 Fq.  op: 0 mul, 1 add, 2 sub, 3 mul via the CIOS cross-check path, 4 from_montgomery, 5 to_montgomery,
  * 6/7 mul / CIOS mul without pre-reduction, 8 a*a - b*b and 9 (-a)(-b) - a(-b) through the fused two-product multiplier,
- * 10 / 11 the inverse of a (0 -> 0) by the binary extended Euclid of the set-up kernels, per lane / on the scalar unit (one wave per element). */
+ * 10 / 11 the inverse of a (0 -> 0) by the binary extended Euclid of the set-up kernels, per lane / on the scalar unit (one wave per element),
+ * 12 (which = 1 only) a^((q + 1) / 4), the square-root candidate of bbg_wire_decode's compressed forms alone: a root of a when a is a
+ * residue, and a value that squares to -a when it is not; which = 0 is BBG_E_INVALID, because r = 1 mod 4 and no single power is a root. */
 int bbg_field_op(bbg_ctx* ctx, int which, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 /* Self test entry of the 29-bit-limb arithmetic, used by tests (like bbg_field_op, but on RAW operands: nothing is pre-reduced, so a lazily
  * reduced value -- limbs above 29 bits, a value of many p -- reaches the device primitive as it is, and the raw result limbs come back).
